@@ -65,6 +65,34 @@ def csrc_sha():
     return h.hexdigest()[:16]
 
 
+DUMP_BYTES = 64 << 20
+DUMP_SEED = 0x6776706D
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: (name, array) pairs as `path`/<name>.npy in float32 (float64 for anything else), in order, at most
+    `budget` bytes in all.  An array that does not fit whole is written as <name>_sample.npy: the rows (pixels, for an
+    (H, W, C) array) at a fixed seeded choice of indices, sorted, with those indices in <name>_sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    left = budget
+    for name, a in arrays:
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes <= left:
+            np.save(os.path.join(path, name + ".npy"), a)
+            left -= a.nbytes
+            continue
+        rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+        k = int(left // (rows.shape[1] * a.itemsize + 8))
+        if k <= 0:
+            continue
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], k, replace=False))
+        np.save(os.path.join(path, name + "_sample.npy"), rows[idx])
+        np.save(os.path.join(path, name + "_sample_rows.npy"), idx.astype(np.float64))
+        left -= k * (rows.shape[1] * a.itemsize + 8)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -108,6 +136,9 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL); gloo only to smoke-test "
                                                       "the N > 1 code path on a one-GPU box together with --single-device")
     ap.add_argument("--single-device", action="store_true", help="every rank uses GPU 0 (smoke test, not a bench line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed (the film's throughput / dx / dy, the per-pixel "
+                         "accumulators, the counters; G-VPM: the SPPM state) as DIR/<name>.npy, 64 MB at most")
     args = ap.parse_args()
     if args.only_timed:
         args.no_cpu_baseline = args.no_parity = args.no_upload_inclusive = args.no_isolated = args.no_other_workloads = True
@@ -256,6 +287,13 @@ def main():
     st = ctx.stats()
     evals = st["evaluations"] - ev0
     kms, klaunches = ctx.kernel_time()
+    if args.dump_outputs and world > 1 and rank == 0:
+        thr, dx, dy = film.cpu().numpy().reshape(3, H, W, 3)  # the frame's film, summed over the ranks
+        dump_outputs(args.dump_outputs, [("throughput", thr), ("dx", dx), ("dy", dy)])
+    elif args.dump_outputs and world == 1:
+        thr, dx, dy = ctx.download_film(K, True)
+        dump_outputs(args.dump_outputs, [("stats", np.array(list(st.values()), np.float64)), ("throughput", thr), ("dx", dx),
+                                         ("dy", dy), ("accum", ctx.download_accum())])
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -490,6 +528,13 @@ def main_technique(args, emit=True):
     evals = st["evaluations"] - ev0
     kms, klaunches = ctx.kernel_time()
     trav_ms, build_ms = ctx.phase_time(1)[0], ctx.phase_time(2)[0]
+    if args.dump_outputs:
+        thr, dx, dy = ctx.download_film(K, True)
+        arrays = [("stats", np.array(list(st.values()), np.float64)), ("throughput", thr), ("dx", dx), ("dy", dy),
+                  ("accum", ctx.download_accum())]
+        if tech == "vpm":
+            arrays += list(zip(("vpm_scale", "vpm_n"), ctx.download_vpm_state()))
+        dump_outputs(args.dump_outputs, arrays)
     nsets_avg = float(np.mean([x["nsets"] for x in inputs]))
     nrec_avg = float(np.mean([x["n"] for x in inputs]))
     P = W * H
@@ -567,6 +612,7 @@ def other_workloads(args):
         a.no_parity = a.no_cpu_baseline = a.no_upload_inclusive = a.no_isolated = a.only_timed = True
         a.photons, a.frame, a.distinct = args.other_photons, args.other_frame, 0  # (0: the workload's stated size)
         a.scene, a.scale, a.technique = "", 0.0, "bre3d"
+        a.dump_outputs = None  # (--dump-outputs: the headline's timed path alone)
         if args.other_frame:
             a.steps = 3
         t0 = time.perf_counter()

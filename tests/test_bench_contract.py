@@ -12,8 +12,32 @@ def test_help_lists_the_contract_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
                          timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--dump-outputs"):
         assert flag in out.stdout
+
+
+def test_dump_outputs_fits_the_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs writes float32 / float64 arrays; what does not fit the budget whole is a seeded sample of its rows,
+    the same rows on every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    small, big = rng.random(5), rng.random((40, 30, 27)).astype(np.float32)
+    budget = small.nbytes + big.nbytes // 4
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("counts", np.arange(5, dtype=np.uint64)), ("small", small), ("big", big)],
+                           budget=budget)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["big_sample.npy", "big_sample_rows.npy", "counts.npy", "small.npy"], names
+    assert sum(os.path.getsize(tmp_path / "a" / n) - 128 for n in names) <= budget  # (128: an .npy header)
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    assert np.array_equal(np.load(tmp_path / "a" / "counts.npy"), np.arange(5)) and np.array_equal(np.load(tmp_path / "a" / "small.npy"), small)
+    rows = np.load(tmp_path / "a" / "big_sample_rows.npy").astype(np.int64)
+    assert len(rows) > 0 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "big_sample.npy"), big.reshape(-1, 27)[rows])
 
 
 def test_json_line_has_the_contract_keys():

@@ -82,3 +82,25 @@ def test_headline_run_carries_the_other_workloads():
             assert k in o, (w, k)
         assert o["kernel"] == kern and o["value"] > 0 and o["ms_per_step"] > 0 and o["evaluations"] > 0
         assert o["workload"].startswith("custom") and o["csrc_sha"] == d["config"]["csrc_sha"]
+
+
+@pytest.mark.parametrize("wl,extra", [
+    ("c2", ["--frame", "96", "--photons", "50000"]),
+    ("c1", ["--frame", "64", "--photons", "20000"]),
+])
+def test_dump_outputs_writes_the_last_step(tmp_path, wl, extra):
+    """--dump-outputs: the film, the accumulators and the counters of the timed path's last step, in float32 / float64 --
+    the counters those of the line, the film the one the accumulators of the same step make."""
+    import numpy as np
+    d = run_bench("--workload", wl, "--steps", "3", "--warmup", "1", "--only-timed", "--dump-outputs", str(tmp_path), *extra)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    names = sorted(os.listdir(tmp_path))
+    want = ["accum.npy", "dx.npy", "dy.npy", "stats.npy", "throughput.npy"] + (["vpm_n.npy", "vpm_scale.npy"] if wl == "c1" else [])
+    assert names == sorted(want), names
+    assert sum(os.path.getsize(tmp_path / n) for n in names) <= 64 << 20
+    a = {n[:-4]: np.load(tmp_path / n) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["stats"][0] == d["config"]["evaluations"] > 0
+    H, W = d["config"]["frame"][1], d["config"]["frame"][0]
+    assert a["throughput"].shape == a["dx"].shape == a["dy"].shape == (H, W, 3) and a["accum"].shape == (H, W, 27)
+    assert np.abs(a["throughput"]).max() > 0 and np.abs(a["accum"]).max() > 0 and np.isfinite(a["accum"]).all()

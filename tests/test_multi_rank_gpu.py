@@ -107,22 +107,38 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did():
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["value"] > 0 and line["steps"] == 2
 
 
-def test_bench_eight_ranks_run_to_completion_on_one_gpu():
-    """The driver's 8-GPU launch is `python -m torch.distributed.run --nproc-per-node 8 bench.py --gpus 8 ...`: the same
-    command here with the eight ranks on GPU 0 over gloo and a small frame, so that the driver's run is not the first
-    8-rank run of this code (sharding by 8, the film all-reduce, the max-over-ranks timing, rank 0's line)."""
-    out = _launch(8, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--backend", "gloo",
-                  "--single-device", "--frame", "128", "--photons", "40000", "--distinct", "2", timeout=900)
+def _bench_ranks(n, single_device):
+    """`python -m torch.distributed.run --nproc-per-node n bench.py --gpus n ...` over gloo at a small frame (sharding by n,
+    the film all-reduce, the max-over-ranks timing, rank 0's line); every evaluation of the frame is counted once: the n
+    shards' counts add up to a one-rank run's."""
+    out = _launch(n, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--backend", "gloo",
+                  *(["--single-device"] if single_device else []), "--frame", "128", "--photons", "40000", "--distinct", "2",
+                  timeout=900)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1  # rank 0 prints, nobody else
     line = json.loads(lines[0])
-    assert line["n_gpus"] == 8 and line["scaling"] == "strong" and line["value"] > 0 and line["steps"] == 2
-    assert line["config"]["frame"] == [128, 128] and line["config"]["pixels_per_gpu"] == 128 * 128 / 8
-    assert "round-robin over 8 ranks" in line["config"]["sharding"]
-    # every evaluation of the frame is counted once: the eight shards' counts add up to a one-rank run's
+    assert line["n_gpus"] == n and line["scaling"] == "strong" and line["value"] > 0 and line["steps"] == 2
+    assert line["config"]["frame"] == [128, 128] and line["config"]["pixels_per_gpu"] == 128 * 128 / n
+    assert f"round-robin over {n} ranks" in line["config"]["sharding"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c4", "--steps", "2", "--warmup", "1",
                           "--frame", "128", "--photons", "40000", "--distinct", "2", "--only-timed"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert one.returncode == 0, one.stderr[-2000:]
     l1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
     assert l1["config"]["evaluations"] == line["config"]["evaluations"]
+
+
+def test_bench_four_ranks_run_to_completion_on_one_gpu():
+    """More than two ranks on GPU 0: four ranks and this process stay within the six processes a shared GPU
+    may host."""
+    _bench_ranks(4, single_device=True)
+
+
+def test_bench_eight_ranks_run_to_completion_on_one_gpu():
+    """The driver's 8-GPU launch is `python -m torch.distributed.run --nproc-per-node 8 bench.py --gpus 8 ...`: the same
+    command with one rank per GPU, so that the driver's run is not the first 8-rank run of this code.  Eight ranks no
+    longer share GPU 0 as the name says: a shared GPU hosts at most six processes (four ranks on one GPU: the test above)."""
+    n = _gpu_count()
+    if n < 8:
+        pytest.skip(f"needs 8 GPUs (one per rank), found {n}")
+    _bench_ranks(8, single_device=False)
