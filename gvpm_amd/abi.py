@@ -143,6 +143,12 @@ PHOTON_CHAIN_DTYPE = np.dtype([("pos", np.float32, 3), ("parent_pdf", np.float32
                                ("parent_rr", np.float32), ("flags", np.uint32)])
 EMITTER_ENTRY_DTYPE = np.dtype([("prefix_w", np.float32, 3), ("parent_rr", np.float32), ("parent_n", np.float32, 3), ("parent_g", np.float32)])
 assert PHOTON_EMIT_DTYPE.itemsize == 48 and PHOTON_CHAIN_DTYPE.itemsize == 40 and EMITTER_ENTRY_DTYPE.itemsize == 32
+GVPM_LINKED_MAGIC = 0x4C4E4B31
+GVPM_LINKED_FULL, GVPM_LINKED_EMIT, GVPM_LINKED_CHAIN = 0, 1, 2
+LINKED_HEADER_DTYPE = np.dtype([(k, np.uint32) for k in (
+    "magic", "n", "n_full", "n_emit", "n_chain", "n_emitters", "off_kinds", "off_groups", "off_emitters", "off_full", "off_emit",
+    "off_chain", "bytes")] + [("reserved", np.uint32, 3)])
+assert LINKED_HEADER_DTYPE.itemsize == 64
 RAY_PACKED_DTYPE = np.dtype([
     ("o", np.float32, 3), ("len", np.float32), ("d", np.float32, 3), ("pdf", np.float32), ("eye", np.float32, 3),
     ("jacobian", np.float32), ("gop", np.float32)])

@@ -383,6 +383,11 @@ struct gvpm_context {
   // photons: raw upload (owned copies or borrowed device pointers) and the built grid
   gvpm_photon_soa rawDev;  // device pointers
   uint32_t nph = 0;
+  // what the last gather read (decoded, in upload order): gvpm_download_photons / gvpm_download_camera_beams (tests)
+  gvpm_photon_soa gatheredPh{};
+  const gvpm_camera_ray *gatheredRays = nullptr;
+  uint32_t gatheredSets = 0;
+  bool haveGathered = false;
   bool havePhotons = false, photonsDirty = false;
   bool nearOverflow = false;
   size_t nearExtWant = 0;         // entries the near-occluder extension lists asked for so far

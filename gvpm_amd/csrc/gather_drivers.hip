@@ -1605,6 +1605,11 @@ static int gatherEntry(gvpm_context *h, int it, uint64_t nb_paths, bool primal) 
     }
     h->rayWait = false;
   }
+  h->gatheredPh = h->rawDev;
+  h->gatheredPh.n = h->nph;
+  h->gatheredRays = h->raysDev;
+  h->gatheredSets = h->nsets;
+  h->haveGathered = true;
   int rc;
   switch (h->cfg.vol_technique) {
     case GVPM_VOL_BRE2D:

@@ -925,6 +925,8 @@ struct VpmFindLds {
   uint32_t rowStart[VPM_ROWS][64];
   uint16_t rowOff16[VPM_ROWS - 1][64];  // rows 1 ..: row 0 starts its sample's list
   uint32_t found[64];                   // photons inside the query sphere | edge << 24
+                                        // (24 bits hold it: at most VPM_ROWS x ROW_LIMIT = 589 815 candidates a query -- a
+                                        // longer row sends the batch to the fused kernel)
   static constexpr uint32_t ROW_LIMIT = 0xFFFFu;
   __device__ __forceinline__ void initSample(int lane, uint32_t e) { found[lane] = e << 24; }
   __device__ __forceinline__ uint32_t edgeOf(uint32_t b) const { return found[b] >> 24; }

@@ -17,6 +17,9 @@ static const char *validateParams(const gvpm_params *p) {
   if (p->max_depth <= 1 && p->max_depth != -1 && p->max_depth != 0) return "Maximum depth must be set to \"2\" or higher!";
   if (!(p->bsphere_radius > 0.f)) return "bsphere_radius must be positive";
   if (!(p->epsilon > 0.f) || !(p->shadow_epsilon > 0.f)) return "epsilon / shadow_epsilon must be positive";
+  // the SPPM update N' = N + alpha M, scale' = scale (N + alpha M) / (N + M) only ever shrinks a scale for alpha in (0, 1]:
+  // G-VPM sizes its grid from a host-side bound that never grows (gatherVPM, vpmScaleBound)
+  if (!std::isfinite(p->alpha) || !(p->alpha > 0.f) || p->alpha > 1.f) return "alpha must be in (0, 1]";
   if (p->vol_technique == GVPM_VOL_PLANE0D && p->min_depth < 2) return "Impossible to use plane with minDepth smaller than 2";
   if (!p->no_medium_shift) return "noMediumShift=false is not supported (shiftPhotonMedium is SAssert(false))";
   return nullptr;
@@ -478,7 +481,9 @@ int gvpm_get_stats(gvpm_context *h, gvpm_stats *out) {
   // reserved[0]: kind of the last G-BRE grid << 56 | optimistic steps the build refused (24 bits) << 32 | its cells
   out->reserved[0] = ((uint64_t)h->lastGridMode << 56) | ((uint64_t)(h->optRefused & 0xFFFFFFu) << 32) | (uint64_t)h->lastGridCells;
   out->reserved[1] = v[6];
-  if (v[6]) return fail(h, GVPM_ERR_STATE, "packed photon records named materials beyond the uploaded table (decoded as black)");
+  if (v[6])
+    return fail(h, GVPM_ERR_STATE, "packed photon records were malformed (a material or emitter index beyond its table, or a "
+                                   "linked blob's kinds / group bases inconsistent): those photons were decoded as black or zero");
   // the planner's bound on an item's pair region is exact: a dropped pair means a biased image, not a slow one
   if (v[7]) return fail(h, GVPM_ERR_STATE, "pairs or deferred shifts were dropped (the G-BRE planner's bound violated, or the exact pass's lists full)");
   return GVPM_OK;

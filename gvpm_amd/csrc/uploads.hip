@@ -30,7 +30,11 @@ __global__ __launch_bounds__(256) void unpack_compact_rays_kernel(gvpm_sensor se
 }
 
 // linked records (pack_codec.h): first pass -- a wave takes 64 consecutive photons; the index of a photon's record within
-// its kind's array is the group's base + the lanes of that kind below it
+// its kind's array is the group's base + the lanes of that kind below it.  The header was checked on the host
+// (linkedHeaderOk); the body is not trusted: a kind 3, or a group whose bases are not the running counts -- base + its
+// records of the kind = the next group's base (the last group's: the header's count), bases of group 0 zero -- is
+// REPORTED (gvpm_get_stats fails, as gvpm_unpack_photons_linked refuses the blob) and decodes as a zero record; no record
+// index at or beyond its kind's count is ever read, whatever the bytes say
 __global__ __launch_bounds__(256) void unpack_linked_kernel(const unsigned char *__restrict__ blob, const gvpm_material *__restrict__ table,
                                                             uint32_t table_n, gvpm_photon_soa dst, unsigned long long *bad) {
   const gvpm_linked_header hd = *reinterpret_cast<const gvpm_linked_header *>(blob);
@@ -42,19 +46,34 @@ __global__ __launch_bounds__(256) void unpack_linked_kernel(const unsigned char 
   const unsigned long long below = (1ull << lane) - 1ull;
   const unsigned long long mF = __ballot(kind == GVPM_LINKED_FULL), mE = __ballot(kind == GVPM_LINKED_EMIT), mC = __ballot(kind == GVPM_LINKED_CHAIN);
   if (!live) return;
-  const uint2 base = reinterpret_cast<const uint2 *>(blob + hd.off_groups)[i >> 6];
+  const uint2 *groups = reinterpret_cast<const uint2 *>(blob + hd.off_groups);
+  const uint32_t g = i >> 6, first = i & ~63u;
+  const uint2 base = groups[g];
+  const uint2 next = g + 1u < (hd.n + 63u) >> 6 ? groups[g + 1u] : make_uint2(hd.n_full, hd.n_emit);
+  const bool groupOk = (uint64_t)base.x + (uint64_t)__popcll(mF) == next.x && (uint64_t)base.y + (uint64_t)__popcll(mE) == next.y &&
+                       (uint64_t)base.x + base.y <= first;
+  bool ok = groupOk;
   if (kind == GVPM_LINKED_FULL) {
-    const gvpm_photon_packed &r = reinterpret_cast<const gvpm_photon_packed *>(blob + hd.off_full)[base.x + (uint32_t)__popcll(mF & below)];
-    if (r.material >= table_n) atomicAdd(bad, 1ull);
+    const uint32_t j = base.x + (uint32_t)__popcll(mF & below);
+    ok = ok && j < hd.n_full;
+    gvpm_photon_packed r{};
+    if (ok) r = reinterpret_cast<const gvpm_photon_packed *>(blob + hd.off_full)[j];
+    if (!ok || r.material >= table_n) atomicAdd(bad, 1ull);
     unpackPhoton(r, table, table_n, dst, i);
   } else if (kind == GVPM_LINKED_EMIT) {
-    const gvpm_photon_emit &r = reinterpret_cast<const gvpm_photon_emit *>(blob + hd.off_emit)[base.y + (uint32_t)__popcll(mE & below)];
-    if ((r.flags >> 16) >= hd.n_emitters) atomicAdd(bad, 1ull);
+    const uint32_t j = base.y + (uint32_t)__popcll(mE & below);
+    ok = ok && j < hd.n_emit;
+    gvpm_photon_emit r{};
+    if (ok) r = reinterpret_cast<const gvpm_photon_emit *>(blob + hd.off_emit)[j];
+    if (!ok || (r.flags >> 16) >= hd.n_emitters) atomicAdd(bad, 1ull);
     unpackEmit(r, reinterpret_cast<const gvpm_emitter_entry *>(blob + hd.off_emitters), hd.n_emitters, dst, i);
   } else {
-    const uint32_t cbase = (i & ~63u) - base.x - base.y;
-    const gvpm_photon_chain &r = reinterpret_cast<const gvpm_photon_chain *>(blob + hd.off_chain)[cbase + (uint32_t)__popcll(mC & below)];
-    if ((r.flags >> 16) >= table_n || i == 0u) atomicAdd(bad, 1ull);
+    // (kind 3 included: its chain index would collide with a real chain record's)
+    const uint32_t j = first - base.x - base.y + (uint32_t)__popcll(mC & below);
+    ok = ok && kind == GVPM_LINKED_CHAIN && j < hd.n_chain;
+    gvpm_photon_chain r{};
+    if (ok) r = reinterpret_cast<const gvpm_photon_chain *>(blob + hd.off_chain)[j];
+    if (!ok || (r.flags >> 16) >= table_n || i == 0u) atomicAdd(bad, 1ull);
     unpackChainOwn(r, table, table_n, dst, i);
   }
 }
@@ -174,29 +193,43 @@ int gvpm_unpack_photons(const gvpm_photon_packed *src, uint64_t n, const gvpm_ma
 }
 
 // ---- linked photon records (include/gvpm_hip.h) ----
-static size_t align16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+static uint64_t align16(uint64_t x) { return (x + 15u) & ~(uint64_t)15u; }
+// the offsets of a blob's parts and its size, {kinds, groups, emitters, full, emit, chain, bytes}, in 64 bits: a header
+// whose counts need more than its uint32 fields hold is not a blob (linkedHeaderOk)
+static void linkedLayout64(const gvpm_linked_header &hd, uint64_t o[7]) {
+  uint64_t off = sizeof(gvpm_linked_header);
+  o[0] = off;
+  off = align16(off + (((uint64_t)hd.n + 15u) / 16u) * 4u);
+  o[1] = off;
+  off = align16(off + (((uint64_t)hd.n + 63u) / 64u) * 8u);
+  o[2] = off;
+  off = align16(off + (uint64_t)hd.n_emitters * sizeof(gvpm_emitter_entry));
+  o[3] = off;
+  off = align16(off + (uint64_t)hd.n_full * sizeof(gvpm_photon_packed));
+  o[4] = off;
+  off = align16(off + (uint64_t)hd.n_emit * sizeof(gvpm_photon_emit));
+  o[5] = off;
+  o[6] = align16(off + (uint64_t)hd.n_chain * sizeof(gvpm_photon_chain));
+}
+// (the packer's blobs: at most 2^25 photons and 1024 emitters, every offset below 2^32)
 static void linkedLayout(gvpm_linked_header &hd) {
-  size_t off = sizeof(gvpm_linked_header);
-  hd.off_kinds = (uint32_t)off;
-  off = align16(off + (((size_t)hd.n + 15u) / 16u) * 4u);
-  hd.off_groups = (uint32_t)off;
-  off = align16(off + (((size_t)hd.n + 63u) / 64u) * 8u);
-  hd.off_emitters = (uint32_t)off;
-  off = align16(off + (size_t)hd.n_emitters * sizeof(gvpm_emitter_entry));
-  hd.off_full = (uint32_t)off;
-  off = align16(off + (size_t)hd.n_full * sizeof(gvpm_photon_packed));
-  hd.off_emit = (uint32_t)off;
-  off = align16(off + (size_t)hd.n_emit * sizeof(gvpm_photon_emit));
-  hd.off_chain = (uint32_t)off;
-  off = align16(off + (size_t)hd.n_chain * sizeof(gvpm_photon_chain));
-  hd.bytes = (uint32_t)off;
+  uint64_t o[7];
+  linkedLayout64(hd, o);
+  hd.off_kinds = (uint32_t)o[0];
+  hd.off_groups = (uint32_t)o[1];
+  hd.off_emitters = (uint32_t)o[2];
+  hd.off_full = (uint32_t)o[3];
+  hd.off_emit = (uint32_t)o[4];
+  hd.off_chain = (uint32_t)o[5];
+  hd.bytes = (uint32_t)o[6];
 }
 size_t gvpm_linked_photons_bound(uint64_t n) {
   gvpm_linked_header hd{};
   hd.n = hd.n_full = (uint32_t)std::min<uint64_t>(n, 0x3FFFFFFFull);
   hd.n_emitters = 1024u;
-  linkedLayout(hd);
-  return (size_t)hd.bytes + 64u;
+  uint64_t o[7];
+  linkedLayout64(hd, o);
+  return (size_t)o[6] + 64u;
 }
 
 int gvpm_pack_photons_linked(const gvpm_photon_soa *src, void *blob, size_t cap, gvpm_material *table, uint32_t table_cap,
@@ -349,13 +382,16 @@ int gvpm_pack_photons_linked(const gvpm_photon_soa *src, void *blob, size_t cap,
   return GVPM_OK;
 }
 
+// the packer's limit on n, and every offset as the 64-bit layout has it: a uint32 layout wraps for large counts and would
+// agree with a header that wrapped the same way
 static bool linkedHeaderOk(const gvpm_linked_header &hd, size_t bytes) {
-  gvpm_linked_header want = hd;
-  linkedLayout(want);
-  return hd.magic == GVPM_LINKED_MAGIC && (size_t)hd.n_full + hd.n_emit + hd.n_chain == hd.n && want.bytes == hd.bytes &&
-         (size_t)hd.bytes <= bytes && want.off_kinds == hd.off_kinds && want.off_groups == hd.off_groups &&
-         want.off_emitters == hd.off_emitters && want.off_full == hd.off_full && want.off_emit == hd.off_emit &&
-         want.off_chain == hd.off_chain;
+  if (hd.magic != GVPM_LINKED_MAGIC || hd.n > (1u << 25) || (uint64_t)hd.n_full + hd.n_emit + hd.n_chain != hd.n) return false;
+  uint64_t o[7];
+  linkedLayout64(hd, o);
+  const uint32_t have[7] = {hd.off_kinds, hd.off_groups, hd.off_emitters, hd.off_full, hd.off_emit, hd.off_chain, hd.bytes};
+  for (int k = 0; k < 7; ++k)
+    if (o[k] != have[k]) return false;
+  return (uint64_t)hd.bytes <= (uint64_t)bytes;
 }
 
 int gvpm_unpack_photons_linked(const void *blob, size_t bytes, const gvpm_material *table, uint32_t table_n, const gvpm_photon_soa *dst) {
@@ -369,8 +405,11 @@ int gvpm_unpack_photons_linked(const void *blob, size_t bytes, const gvpm_materi
   const gvpm_photon_packed *F = reinterpret_cast<const gvpm_photon_packed *>(B + hd.off_full);
   const gvpm_photon_emit *E = reinterpret_cast<const gvpm_photon_emit *>(B + hd.off_emit);
   const gvpm_photon_chain *Cn = reinterpret_cast<const gvpm_photon_chain *>(B + hd.off_chain);
+  const uint32_t *groups = reinterpret_cast<const uint32_t *>(B + hd.off_groups);
   uint64_t jf = 0, je = 0, jc = 0;
   for (uint64_t i = 0; i < hd.n; ++i) {
+    // the per-64-photon bases the device indexes with ARE the running counts (the device checks the same per group)
+    if ((i & 63u) == 0u && (groups[2 * (i >> 6)] != jf || groups[2 * (i >> 6) + 1] != je)) return GVPM_ERR_INVALID_ARG;
     const uint32_t k = gvpm::linkedKind(kinds, i);
     if (k == GVPM_LINKED_FULL) {
       if (jf >= hd.n_full || F[jf].material >= table_n) return GVPM_ERR_INVALID_ARG;
@@ -992,6 +1031,41 @@ static int uploadSamplesCommon(gvpm_context *h, const gvpm_vpm_sample *smp, uint
   }
   h->nsamples = (uint32_t)n;
   h->haveSamples = true;
+  return GVPM_OK;
+}
+
+// ---- read-back of what the last gather decoded (tests and debugging) ----
+static int syncAllStreams(gvpm_context *h) {
+  for (hipStream_t s : {h->copyStream, h->stream, h->streamB, h->streamC, h->streamA2})
+    if (s) HIP_TRY(h, hipStreamSynchronize(s));
+  return GVPM_OK;
+}
+
+int gvpm_download_photons(gvpm_context *h, const gvpm_photon_soa *dst) {
+  CHECK_H(h);
+  if (!h->haveGathered) return fail(h, GVPM_ERR_STATE, "gvpm_download_photons: no gather yet");
+  const gvpm_photon_soa &s = h->gatheredPh;
+  if (!dst || dst->n != s.n) return fail(h, GVPM_ERR_INVALID_ARG, "gvpm_download_photons: dst->n must be the gathered photon count");
+  const void *from[14] = {s.pos, s.wi, s.flux, s.parent_pos, s.parent_n, s.prefix_w, s.parent_scat, s.parent_wi,
+                          s.parent_pdf, s.edge_pdf, s.parent_rr, s.parent_g, s.flags, s.path_id};
+  const void *to[14] = {dst->pos, dst->wi, dst->flux, dst->parent_pos, dst->parent_n, dst->prefix_w, dst->parent_scat, dst->parent_wi,
+                        dst->parent_pdf, dst->edge_pdf, dst->parent_rr, dst->parent_g, dst->flags, dst->path_id};
+  for (int k = 0; k < 14; ++k)
+    if (s.n && !to[k]) return fail(h, GVPM_ERR_INVALID_ARG, "gvpm_download_photons: null destination array");
+  if (int rc = syncAllStreams(h)) return rc;
+  for (int k = 0; k < 14 && s.n; ++k)
+    HIP_TRY(h, hipMemcpy(const_cast<void *>(to[k]), from[k], (size_t)s.n * (k < 8 ? 12 : 4), hipMemcpyDeviceToHost));
+  return GVPM_OK;
+}
+
+int gvpm_download_camera_beams(gvpm_context *h, gvpm_camera_ray *dst, uint64_t cap, uint64_t *n) {
+  CHECK_H(h);
+  if (!h->haveGathered) return fail(h, GVPM_ERR_STATE, "gvpm_download_camera_beams: no gather yet");
+  if (!n || (cap && !dst)) return fail(h, GVPM_ERR_INVALID_ARG, "gvpm_download_camera_beams: null n or dst");
+  *n = h->gatheredSets;
+  const uint64_t m = std::min<uint64_t>(cap, h->gatheredSets);
+  if (int rc = syncAllStreams(h)) return rc;
+  if (m) HIP_TRY(h, hipMemcpy(dst, h->gatheredRays, (size_t)m * 5 * sizeof(gvpm_camera_ray), hipMemcpyDeviceToHost));
   return GVPM_OK;
 }
 

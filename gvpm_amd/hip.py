@@ -35,6 +35,7 @@ SYMBOLS = [
     "gvpm_enable_host_shifts", "gvpm_download_shift_requests", "gvpm_upload_host_shifts",
     "gvpm_upload_sensor", "gvpm_pack_camera_beams_compact", "gvpm_unpack_camera_beams_compact",
     "gvpm_upload_camera_beams_compact", "gvpm_prefetch_camera_beams_compact", "gvpm_upload_bsdfs", "gvpm_gather_primal",
+    "gvpm_download_photons", "gvpm_download_camera_beams",
 ]
 
 
@@ -124,6 +125,8 @@ def lib():
         L.gvpm_unpack_camera_beams_compact.argtypes = [C.POINTER(abi.Sensor), vp, C.c_uint64, vp]
         L.gvpm_upload_camera_beams_compact.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
         L.gvpm_prefetch_camera_beams_compact.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
+        L.gvpm_download_photons.argtypes = [vp, C.POINTER(abi.PhotonSoA)]
+        L.gvpm_download_camera_beams.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gvpm_host_alloc_photons.argtypes = [C.c_uint64, C.POINTER(abi.PhotonSoA), C.POINTER(vp)]
         L.gvpm_host_free.argtypes = [vp]
         L.gvpm_prefetch_photons.argtypes = [vp, C.POINTER(abi.PhotonSoA)]
@@ -608,6 +611,23 @@ class Context:
 
     def synchronize(self):
         self._check(lib().gvpm_synchronize(self._h))
+
+    # read-back of decoded inputs (tests and debugging)
+    def download_photons(self, n):
+        """the photons the last gather read, as the device decoded them (abi.Photons of n, the gather's photon count)"""
+        ph = abi.Photons(n)
+        soa = ph.soa()
+        self._check(lib().gvpm_download_photons(self._h, C.byref(soa)))
+        return ph
+
+    def download_camera_beams(self):
+        """the camera rays the last gather read, (nsets, 5) CAMERA_RAY_DTYPE in the device's set order"""
+        n = C.c_uint64(0)
+        self._check(lib().gvpm_download_camera_beams(self._h, None, 0, C.byref(n)))
+        rays = np.zeros((n.value, 5), abi.CAMERA_RAY_DTYPE)
+        if n.value:
+            self._check(lib().gvpm_download_camera_beams(self._h, rays.ctypes.data, n.value, C.byref(n)))
+        return rays
 
     def comm_init(self, id128, rank, world):
         buf = (C.c_char * 128).from_buffer_copy(id128)

@@ -153,7 +153,7 @@ typedef struct gvpm_params {
   int32_t visibility_as_written;/* 1: shadow ray maxt = lProj*ShadowEpsilon as
                                    written at shift_volume_photon.cpp:396;
                                    0: lProj*(1-ShadowEpsilon)                  */
-  float alpha;                  /* alpha (radius reduction)                    */
+  float alpha;                  /* alpha (radius reduction), in (0, 1]         */
   float initial_scale_volume;   /* initialScaleVolume                          */
   float bsphere_radius;         /* m_smokeAABB.getBSphere().radius             */
   float epsilon;                /* Epsilon, include/mitsuba/core/constants.h   */
@@ -582,6 +582,16 @@ int gvpm_upload_camera_beams_compact(gvpm_context *h, const gvpm_beam_set_compac
                                      const gvpm_beam_set_packed *full, uint64_t n_full);
 int gvpm_prefetch_camera_beams_compact(gvpm_context *h, const gvpm_beam_set_compact *compact, uint64_t n_compact,
                                        const gvpm_beam_set_packed *full, uint64_t n_full);
+
+/* ---- read-back of decoded inputs (for tests and debugging; not part of a render loop) --------------------------------*/
+/* What the LAST gather read, as the device decoded it, before the next upload into the same staging slot.  Both wait for
+ * every stream of the handle, then copy.  GVPM_ERR_STATE before the first gather.
+ * gvpm_download_photons: the photon SoA in upload order; dst holds 14 writable host arrays of dst->n elements, and dst->n
+ *   must be that gather's photon count (GVPM_ERR_INVALID_ARG otherwise).
+ * gvpm_download_camera_beams: the camera rays, five per set, in the device's set order (compact sets first, then the full
+ *   ones: new_index of gvpm_pack_camera_beams_compact); min(cap, *n) sets are copied, *n = the gather's set count.       */
+int gvpm_download_photons(gvpm_context *h, const gvpm_photon_soa *dst);
+int gvpm_download_camera_beams(gvpm_context *h, gvpm_camera_ray *dst, uint64_t cap, uint64_t *n);
 
 /* ---- manifold shifts through the host (first slice) ----------------------------------------*/
 /* A photon whose shift type is 3 (EManifoldShift: a specular chain between the photon and the vertex it can be re-connected

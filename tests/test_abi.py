@@ -66,6 +66,12 @@ def test_create_reports_errors_without_gpu():
     p = SynthScene("cbox", 8, 8).params()
     p.vol_technique = abi.GVPM_VOL_BRE2D  # useShiftNull with a 2D kernel: GPMConfig::load raises EError
     assert lib.gvpm_create(C.byref(p), 0, C.byref(h)) == abi.GVPM_ERR_UNSUPPORTED
+    # the SPPM radius reduction: alpha in (0, 1] (G-VPM's grid bound assumes scales never grow)
+    for alpha in (0.0, -0.5, 1.0000001, 2.0, float("nan"), float("inf")):
+        q = SynthScene("cbox", 8, 8).params()
+        q.vol_technique = abi.GVPM_DISTANCE
+        q.alpha = alpha
+        assert lib.gvpm_create(C.byref(q), 0, C.byref(h)) == abi.GVPM_ERR_INVALID_ARG, alpha
     assert lib.gvpm_gather(None, 1, 1) == abi.GVPM_ERR_INVALID_ARG
     assert lib.gvpm_last_error(None) == b"null handle"
 

@@ -11,7 +11,8 @@ from test_parity_gpu import l2, TOL
 pytestmark = pytest.mark.gpu
 
 
-def device_vpm(c, iters=1, p=None, rays=None, exact=True):
+def device_vpm(c, iters=1, p=None, rays=None, exact=True, nph=None):
+    """nph: the photon count of every iteration after the first (default: the first's)"""
     p = c.p if p is None else p
     ctx = hip.Context(p, device=0)
     ctx.upload_scene(*c.tris)
@@ -25,7 +26,7 @@ def device_vpm(c, iters=1, p=None, rays=None, exact=True):
         if it == 1:
             ph, nb, r, smp = c.ph, c.nb, (c.rays if rays is None else rays), c.samples
         else:
-            ph, nb = c.sc.shoot_photons(it, c.ph.n)
+            ph, nb = c.sc.shoot_photons(it, c.ph.n if nph is None else nph[it - 2])
             r, smp = c.sc.camera_beams_and_vpm_samples(it, p.nb_camera_samples)
         ctx.upload_photons(ph)
         ctx.upload_camera_beams(r)
@@ -76,6 +77,18 @@ def test_vpm_thin_medium():
 def test_vpm_three_iterations_sppm_state():
     c = make_vpm_case("cbox", 24, 20, 30000, 5.0, nb=8)
     device_vpm(c, iters=3)
+
+
+@pytest.mark.parametrize("alpha", [0.05, 1.0])
+def test_vpm_alpha_at_the_ends_of_its_range(alpha):
+    """G-VPM sizes its grid from a host-side bound on the largest scale that only ever shrinks, valid for alpha in (0, 1]
+    (gvpm_create refuses other values).  At 0.05 the scales of the pixels that find photons shrink fast and the bound stays
+    far above them, step after step; at 1.0 the scales never change and the cells sit exactly at the bound.  The photon
+    count changes from step to step."""
+    c = make_vpm_case("cbox", 24, 20, 30000, 5.0, nb=6)
+    p = c.p.copy()
+    p.alpha = alpha
+    device_vpm(c, iters=6, p=p, nph=[12000, 45000, 20000, 60000, 8000])
 
 
 @pytest.mark.parametrize("kw", [dict(use_mis=0), dict(use_shift_null=0), dict(power_heuristic=1), dict(max_depth=3),
