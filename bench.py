@@ -8,6 +8,11 @@ HBM.  Metric: M photon-gather+shift evaluations / s.
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints one JSON line.  --full adds the legs
+beside the headline (one GPU): the CPU baseline (`cpu_baseline`), step 1 against the fp64 oracle (`parity`), the same steps
+fed from host memory (`upload_inclusive`), the dominant kernel on one stream (`roofline.kernel_isolated_ms`) and, behind C2,
+C1 / C3 / C5 (`other_workloads`).
+
 Workloads (BASELINE.json `configs`):
   N = 1  configs[1] "C2": S-cbox + homogeneous medium, G-BRE 3D, 512x512, 1 M photons / iteration.
   N > 1  configs[3] "C4": S-fogroom, G-BRE 3D, 1024x1024, 4 M photons / iteration, STRONG scaling: the frame's 4x4-pixel
@@ -93,7 +98,9 @@ def dump_outputs(path, arrays, budget=DUMP_BYTES):
         left -= k * (rows.shape[1] * a.itemsize + 8)
 
 
-def main():
+def parse_args(argv=None):
+    """The command line, with the legs beside the headline resolved into the --no-* flags: a run without --full (or with
+    --only-timed) sets every one of them."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=16)
@@ -112,10 +119,15 @@ def main():
                          "--workload c3, the 1D beam kernel instead of the 3D one (probe)")
     ap.add_argument("--scale", type=float, default=0.0, help="initialScaleVolume (0: the workload's, 1.0 for c2 / c4)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="c1 / c3 / c5: CPU time the all-core oracle sample is sized for (a pilot window sets the size)")
+                    help="--full, c1 / c3 / c5: CPU time the all-core oracle sample is sized for (a pilot window sets the size)")
     ap.add_argument("--distinct", type=int, default=0, help="distinct pre-generated iterations, cycled (0: the workload's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the CPU baseline, the oracle parity of step 1, the "
+                         "PCIe-inclusive leg, the single-stream kernel (kernel_isolated_ms) and C1 / C3 / C5 behind C2; each "
+                         "--no-* flag drops one of them.  Without it a run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints its line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-iters", type=int, default=8, help="iterations of the workload the all-core CPU baseline is timed on")
+    ap.add_argument("--cpu-iters", type=int, default=8, help="--full: iterations of the workload the all-core CPU baseline is timed on")
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle comparison of step 1 (parity_l2 / relMSE)")
     ap.add_argument("--no-upload-inclusive", action="store_true", help="skip the PCIe-inclusive leg")
     ap.add_argument("--no-isolated", action="store_true", help="skip the single-stream leg (kernel_isolated_ms)")
@@ -124,7 +136,8 @@ def main():
     ap.add_argument("--no-other-workloads", action="store_true",
                     help="skip the C1 / C3 / C5 leg of the headline run (`other_workloads` in the JSON line)")
     ap.add_argument("--only-timed", action="store_true",
-                    help="profiling runs: nothing but warm-up + the timed steps touches the GPU (implies the four --no-* flags)")
+                    help="profiling runs: nothing but warm-up + the timed steps touches the GPU, as without --full (with it: "
+                         "the five --no-* flags at once)")
     ap.add_argument("--emulate-gpus", type=int, default=0,
                     help="single-GPU run of rank 0's shard of an N-GPU frame (sizing probe); not a bench line")
     ap.add_argument("--device-gen", action="store_true",
@@ -139,11 +152,16 @@ def main():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what they computed (the film's throughput / dx / dy, the per-pixel "
                          "accumulators, the counters; G-VPM: the SPPM state) as DIR/<name>.npy, 64 MB at most")
-    args = ap.parse_args()
-    if args.only_timed:
+    args = ap.parse_args(argv)
+    if args.only_timed or not args.full:
         args.no_cpu_baseline = args.no_parity = args.no_upload_inclusive = args.no_isolated = args.no_other_workloads = True
     if args.primal:
         args.no_cpu_baseline = args.no_upload_inclusive = args.no_isolated = True
+    return args
+
+
+def main():
+    args = parse_args()
     if args.workload in ("c1", "c3", "c5"):
         return main_technique(args)
     if args.scale == 0.0:

@@ -3,7 +3,7 @@
 out=${1:-gpurun_out/ab}; mkdir -p $out
 run() { # name, env...
   name=$1; shift
-  env "$@" python bench.py --no-cpu-baseline --no-parity --no-upload-inclusive --distinct 4 --steps 16 --warmup 3 2> $out/$name.err | python -c "
+  env "$@" python bench.py --full --no-cpu-baseline --no-parity --no-upload-inclusive --distinct 4 --steps 16 --warmup 3 2> $out/$name.err | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('%-28s %8.1f Mev/s  step %.3f ms  eval %.3f  iso %.3f  trav %.3f  build %.3f' % ('$name', d['value'], d['ms_per_step'], r['kernel_avg_ms'], r.get('kernel_isolated_ms',0), r['traverse_avg_ms'], r['build_avg_ms']))" | tee -a $out/summary.txt

@@ -1,7 +1,7 @@
 #!/bin/bash
 # bash scripts/collect_profiles.sh <round tag, e.g. r04> [workloads: c2 c1 c3 c5]  (on the GPU box, from the repo root)
 # For every workload: scripts/profile.sh (kernel statistics pipelined + single stream, four PMC passes, traffic), then the
-# plain bench line with the fresh traffic file in place -> gpurun_out/<round>/, named as profiles/ keeps them.
+# full bench line (--full) with the fresh traffic file in place -> the round's output folder, named as profiles/ keeps them.
 R=$1; shift
 WL=${*:-c2 c1 c3 c5}
 D=$PWD/gpurun_out/$R
@@ -16,7 +16,7 @@ for w in $WL; do
   cp $P/bench_line.json $D/${R}_${w}_profiled_bench_line.json
   cp $P/traffic.json $D/$tj
   cp $P/traffic.json profiles/$tj   # (this box's copy: the bench line below reports `traffic` from it)
-  python3 bench.py $args > $D/${R}_${w}_bench_line.json 2> $D/${R}_${w}_bench.err
+  python3 bench.py --full $args > $D/${R}_${w}_bench_line.json 2> $D/${R}_${w}_bench.err
   tail -c 600 $D/${R}_${w}_bench_line.json
   rm -rf $P/trace $P/trace1 $P/pmc1 $P/pmc2 $P/pmc3 $P/pmc4
 done

@@ -3,7 +3,7 @@
 out=${1:-gpurun_out/shard}; mkdir -p $out; shift
 which=${*:-c2 c2_weak8_rank0 c4_one_gpu c4_strong8_rank0 c4_strong2_rank0 c4_strong4_rank0}
 run() { name=$1; shift
-  python bench.py --no-cpu-baseline --no-parity --no-upload-inclusive ${ISO---no-isolated} --steps 8 --warmup 2 "$@" 2> $out/$name.err | grep '^{' > $out/$name.json
+  python bench.py --full --no-cpu-baseline --no-parity --no-upload-inclusive ${ISO---no-isolated} --steps 8 --warmup 2 "$@" 2> $out/$name.err | grep '^{' > $out/$name.json
   python - $out/$name.json $name <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); r=d['roofline']; c=d['config']

@@ -16,6 +16,26 @@ def test_help_lists_the_contract_flags():
         assert flag in out.stdout
 
 
+def test_legs_beside_the_headline_run_only_with_full():
+    """A plain `--gpus 1 --steps K --warmup W` runs the headline alone; --full turns every leg on, each --no-* flag still
+    drops one, and --only-timed drops them all."""
+    sys.path.insert(0, ROOT)
+    import bench
+    legs = ("no_cpu_baseline", "no_parity", "no_upload_inclusive", "no_isolated", "no_other_workloads")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert not plain.full and all(getattr(plain, k) for k in legs)
+    assert (plain.gpus, plain.steps, plain.warmup, plain.dump_outputs) == (1, 5, 2, None)
+    full = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2", "--full"])
+    assert full.full and not any(getattr(full, k) for k in legs)
+    for k in legs:
+        one = bench.parse_args(["--full", "--" + k.replace("_", "-")])
+        assert [getattr(one, j) for j in legs] == [j == k for j in legs], k
+    assert all(getattr(bench.parse_args(["--full", "--only-timed"]), k) for k in legs)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout
+
+
 def test_dump_outputs_fits_the_budget_with_a_fixed_sample(tmp_path):
     """--dump-outputs writes float32 / float64 arrays; what does not fit the budget whole is a seeded sample of its rows,
     the same rows on every call."""

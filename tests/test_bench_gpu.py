@@ -1,6 +1,6 @@
-"""bench.py on the GPU box, at reduced sizes: every workload's line (c2 the default; c1 / c3 / c5 the G-VPM / G-Beams /
-G-Planes configs) carries the contract keys with `roofline` and `cpu_baseline`, its parity leg agrees with the oracle,
-and the default command line still finishes in minutes."""
+"""bench.py on the GPU box, at reduced sizes: with --full every workload's line (c2 the default; c1 / c3 / c5 the G-VPM /
+G-Beams / G-Planes configs) carries the contract keys with `roofline` and `cpu_baseline`, its parity leg agrees with the
+oracle, and the default command line still finishes in minutes; without --full the line is the headline's alone."""
 import json
 import os
 import subprocess
@@ -46,14 +46,14 @@ def check_line(d, steps):
     ("c5", ["--frame", "64", "--photons", "4000"]),
 ])
 def test_other_workloads_emit_the_same_line(wl, extra):
-    d = run_bench("--workload", wl, "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5", *extra)
+    d = run_bench("--workload", wl, "--steps", "3", "--warmup", "1", "--full", "--cpu-seconds", "0.5", *extra)
     check_line(d, 3)
     assert d["config"]["workload"].startswith("custom")  # reduced sizes are not the BASELINE config: the line says so
     assert d["roofline"]["kernel"] in ("vpm_find_kernel+vpm_eval_kernel", "evaluate_beams2_kernel", "gather_planes_kernel")
 
 
 def test_default_workload_reduced():
-    d = run_bench("--steps", "3", "--warmup", "1", "--frame", "96", "--photons", "50000", "--cpu-iters", "1")
+    d = run_bench("--steps", "3", "--warmup", "1", "--full", "--frame", "96", "--photons", "50000", "--cpu-iters", "1")
     check_line(d, 3)
     assert d["roofline"]["kernel"] == "evaluate_bre_kernel" and "upload_inclusive" in d
     # the PCIe-inclusive leg replays the timed region's iterations (same input sets, same radii): same evaluation count
@@ -67,10 +67,10 @@ def test_default_workload_reduced():
 
 
 def test_headline_run_carries_the_other_workloads():
-    """The default command line times C1 / C3 / C5 behind the headline's legs: one entry per
-    workload with the figures of its own line -- here at reduced sizes, which the entries say."""
-    d = run_bench("--steps", "3", "--warmup", "1", "--frame", "96", "--photons", "50000", "--cpu-iters", "1", "--other-frame", "64",
-                  "--other-photons", "4000")
+    """--full times C1 / C3 / C5 behind the headline's legs: one entry per workload with the
+    figures of its own line -- here at reduced sizes, which the entries say."""
+    d = run_bench("--steps", "3", "--warmup", "1", "--full", "--frame", "96", "--photons", "50000", "--cpu-iters", "1",
+                  "--other-frame", "64", "--other-photons", "4000")
     check_line(d, 3)
     ow = d["other_workloads"]
     assert sorted(ow) == ["c1", "c3", "c5"]
@@ -82,6 +82,28 @@ def test_headline_run_carries_the_other_workloads():
             assert k in o, (w, k)
         assert o["kernel"] == kern and o["value"] > 0 and o["ms_per_step"] > 0 and o["evaluations"] > 0
         assert o["workload"].startswith("custom") and o["csrc_sha"] == d["config"]["csrc_sha"]
+
+
+@pytest.mark.parametrize("wl,extra", [
+    ("c2", ["--frame", "64", "--photons", "20000"]),
+    ("c1", ["--frame", "64", "--photons", "20000"]),
+])
+def test_plain_run_is_the_headline_alone(wl, extra):
+    """Without --full a run is warm-up + timed steps + its line: none of the legs beside the headline, whose figures and
+    counters are those of a --full run of the same command line."""
+    legs = ("cpu_baseline", "parity", "parity_l2", "upload_inclusive", "other_workloads")
+    plain = run_bench("--workload", wl, "--steps", "3", "--warmup", "1", *extra)
+    for k in legs:
+        assert k not in plain, k
+    assert "kernel_isolated_ms" not in plain["roofline"]
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    full = run_bench("--workload", wl, "--steps", "3", "--warmup", "1", "--full", "--cpu-seconds", "0.5", "--cpu-iters", "1",
+                     *extra)
+    assert "cpu_baseline" in full and "parity" in full
+    assert ("upload_inclusive" in full and "kernel_isolated_ms" in full["roofline"]) == (wl == "c2")
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k], k
+    assert plain["stats"] == full["stats"] and plain["config"]["evaluations"] == full["config"]["evaluations"]
 
 
 @pytest.mark.parametrize("wl,extra", [
