@@ -576,8 +576,14 @@ __device__ __forceinline__ void waveLdsSync() {
 // workgroup of 4 waves costs the dispatcher what a workgroup of one wave does, and 22 000 single-wave workgroups per
 // launch were dispatch-bound (2.4 resident waves per SIMD on average where registers and LDS allow 5)
 constexpr int TRAV_WPB = GVPM_TRAV_WPB;
+// waves per SIMD the traversal is compiled for: the hand-off instantiation (the C2 path) needs 95 VGPRs with nothing spilled
+// and takes 5 (round 8: 6 -- 80 -- spills 2); the own-walk one keeps 4 (127 VGPRs; 5 spills 36).  Round 6, one kernel for
+// both paths: 3 -- 147 -- was 2 % slower on the pipelined C2 step than 4 -- 128; 5 -- 96, 60 spilled -- equal
 #ifndef GVPM_TRAV_MINW
-#define GVPM_TRAV_MINW 4  // (128 VGPRs; 3 -- 147 -- is 2 % slower on the pipelined C2 step, 5 -- 96, 60 spilled -- equal)
+#define GVPM_TRAV_MINW 5
+#endif
+#ifndef GVPM_TRAV_OWN_MINW
+#define GVPM_TRAV_OWN_MINW 4
 #endif
 // Work units of the evaluation (round 6).  The planner balances the TRAVERSAL (items of equal staged photons); the pairs an
 // item yields vary by more than ten (C2: mean 450, the items in front of the light 4 500+), and the evaluation took one item per
@@ -602,8 +608,12 @@ struct alignas(16) TravLds {
 };
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-template <int B>
-__global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(GVPM_TRAV_MINW))) void traverse_bre_kernel(GatherArgs a, const uint4 *__restrict__ items,
+// OWN_WALK: the kernel computes each slab step's cell box from its own beams (slabBox), as the planner did; only when the
+// planner hands no boxes over (GatherArgs::planBoxes null: GVPM_PLAN_BOXES=0, or a grid dimension of 1024 or more).  The
+// hand-off instantiation keeps none of TileWalk's per-lane walk state past the set-up (round 8: 95 VGPRs against the own
+// walk's 127, at B = 16).
+template <int B, bool OWN_WALK>
+__global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(OWN_WALK ? GVPM_TRAV_OWN_MINW : GVPM_TRAV_MINW))) void traverse_bre_kernel(GatherArgs a, const uint4 *__restrict__ items,
                                                           const uint2 *__restrict__ itemOff,
                                                           const uint32_t *__restrict__ itemCount, uint32_t *queueHead,
                                                           uint32_t *__restrict__ pairs, uint32_t *__restrict__ pairCnt,
@@ -621,7 +631,8 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(G
   const float r2f = r * r;
   const float eps = a.cfg.epsilon;
   const uint32_t coalesceAt = a.cfg.reserved[3] ? (uint32_t)a.cfg.reserved[3] : 512u;  // photons in a box row set
-  unsigned long long nCand = 0, nOver = 0;
+  unsigned long long nCand = 0;  // wave-uniform
+  uint32_t nOver = 0;
 
   // One item per wave (the grid is the item count: the hardware dispatcher balances the load and, at every workgroup
   // boundary, lets the other streams' kernels in by priority -- persistent waves hold their registers until the whole
@@ -646,13 +657,17 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(G
     // the item's region: one list of up to `cap` photon indices per beam of the tile
     const uint2 reg = itemOff[it];
     const uint32_t cap = reg.y;
-    uint32_t *out = pairs + (size_t)reg.x * 64u + (size_t)b * cap;
+    // (a wave-uniform base and a 32-bit offset per lane, not a 64-bit pointer per lane)
+    uint32_t *const outBase = pairs + (size_t)reg.x * 64u;
+    const uint32_t outOff = (uint32_t)b * cap;
     uint32_t mine = 0;  // hits of this lane's beam so far (equal in the LPB lanes of the beam)
     BaseInfo bi;
     const RayReg base = loadBaseDirect<B>(a, setBase, nb, lane, bi);
     TileWalk w;
     tileSetupFrom(a, base, base.valid, w);
     const bool beamValid = w.beamValid;
+    // the walk's wave-uniform bounds (the hand-off instantiation needs nothing else of TileWalk past this point)
+    const int cA0 = __builtin_amdgcn_readfirstlane(w.cA0), K = __builtin_amdgcn_readfirstlane(w.K);
     const float mint = eps, maxt = base.len - eps;
     // depth + edge within [minDepth, maxDepth] (shift_volume_photon.cpp:670-673) as a window on the photon's depth
     const int dmax = a.cfg.max_depth > 0 ? a.cfg.max_depth - (int)bi.edge : 0x7FFFFFFF;
@@ -704,17 +719,23 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(G
     const bool bundle = a.grid.mode == 1;
     const uint32_t part = bundle ? (item.z >> 8) & 0xFFFu : 0u, parts = bundle ? max(item.z >> 20, 1u) : 1u;
     uint32_t winNo = 0;
-    const int cBeg = max((int)(bundle ? item.z & 0xFFu : item.z), w.cA0), cEnd = min((int)item.w, w.cA1);
-    for (int cA = cBeg; cA <= cEnd; cA += w.K) {
-      const int cAe = min(cA + w.K - 1, cEnd);
+    const int cBeg = max((int)(bundle ? item.z & 0xFFu : item.z), cA0),
+              cEnd = min((int)item.w, __builtin_amdgcn_readfirstlane(w.cA1));
+    for (int cA = cBeg; cA <= cEnd; cA += K) {
+      const int cAe = min(cA + K - 1, cEnd);
       CellBox bx;
-      // the slab's cell box: the planner's (it reduced the tile's footprints to count the box's photons), one load
-      // instead of a footprint per lane, four wave reductions and the cell arithmetic per slab step
-      const uint32_t stepIdx = (uint32_t)(cA - w.cA0) / (uint32_t)w.K;
-      if (a.planBoxes && stepIdx < a.planBoxStride) {
+      if constexpr (OWN_WALK) {
+        if (!slabBox(a, w, cA, cAe, bx)) continue;
+      } else {
+        // the slab's cell box: the planner's (it reduced the tile's footprints to count the box's photons), one load
+        // instead of a footprint per lane, four wave reductions and the cell arithmetic per slab step.  The driver sizes
+        // the boxes for every step a chunk can have: a step beyond them is counted as dropped pairs (an error, not a skip)
+        const uint32_t stepIdx = (uint32_t)(cA - cA0) / (uint32_t)K;
+        if (stepIdx >= a.planBoxStride) {
+          nOver += lane == 0 ? 1u : 0u;
+          continue;
+        }
         if (!unpackCellBox(a.planBoxes[(size_t)chunk * a.planBoxStride + stepIdx], bx)) continue;
-      } else if (!slabBox(a, w, cA, cAe, bx)) {
-        continue;
       }
       const int nranges = (bx.by1 - bx.by0 + 1) * (bx.bz1 - bx.bz0 + 1);
       for (int rbase = 0; rbase < nranges; rbase += 64) {
@@ -722,7 +743,7 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(G
         boxRange(a, bx, rbase + lane, nranges, start, count);
         const uint32_t incl = wave_scan_incl(count, lane);
         const uint32_t excl = incl - count;
-        const uint32_t total = __shfl(incl, 63, 64);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);  // (wave-uniform: the window loop in SGPRs)
         for (uint32_t win = 0; win < total; win += STAGE) {
           if (parts > 1u && (winNo++ % parts) != part) continue;
           // stage [win, win + STAGE) of the concatenated ranges
@@ -853,7 +874,7 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(G
               while (cm) {
                 const uint32_t u = (uint32_t)__ffs(cm) - 1u;
                 cm &= cm - 1u;
-                if (off < cap) out[off] = s.stageIdx[j0 + u];
+                if (off < cap) outBase[outOff + off] = s.stageIdx[j0 + u];
                 else nOver++;
                 ++off;
               }
@@ -886,11 +907,11 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(G
   }
   {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nOver += __shfl_xor(nOver, o, 64);
+    for (int o = 32; o > 0; o >>= 1) nOver += (uint32_t)__shfl_xor((int)nOver, o, 64);
     if (lane == 0 && (nCand | nOver)) {
       unsigned long long *row = statRow(a);
       atomicAdd(&row[1], nCand);
-      if (nOver) atomicAdd(&row[7], nOver);  // must stay 0: the planner's bound is exact
+      if (nOver) atomicAdd(&row[7], (unsigned long long)nOver);  // must stay 0: the planner's bound is exact
     }
   }
 }
@@ -1477,11 +1498,18 @@ void launch_traverse_bre(const GatherArgs &a, int beamsPerWave, const uint4 *ite
                          uint32_t nwaves, bool persistent, hipStream_t stream, uint2 *units, uint32_t *unitCtl, uint32_t unitCap) {
   if (a.nsets == 0 || nwaves == 0) return;
   const uint32_t persist = persistent ? 1u : 0u;
+  const dim3 grid((nwaves + TRAV_WPB - 1) / TRAV_WPB), block(64 * TRAV_WPB);
+#define GVPM_LAUNCH_TRAV(BB, OWN) \
+  hipLaunchKernelGGL((traverse_bre_kernel<BB, OWN>), grid, block, 0, stream, a, items, itemOff, itemCount, queueHead, pairs, pairCnt, \
+                     persist, units, unitCtl, unitCap)
+  // (the driver hands the planner's boxes over whenever it can size them, gather_drivers.hip)
+  const bool own = a.planBoxes == nullptr;
   switch (beamsPerWave) {
-    case 64: hipLaunchKernelGGL(traverse_bre_kernel<64>, dim3((nwaves + TRAV_WPB - 1) / TRAV_WPB), dim3(64 * TRAV_WPB), 0, stream, a, items, itemOff, itemCount, queueHead, pairs, pairCnt, persist, units, unitCtl, unitCap); break;
-    case 32: hipLaunchKernelGGL(traverse_bre_kernel<32>, dim3((nwaves + TRAV_WPB - 1) / TRAV_WPB), dim3(64 * TRAV_WPB), 0, stream, a, items, itemOff, itemCount, queueHead, pairs, pairCnt, persist, units, unitCtl, unitCap); break;
-    default: hipLaunchKernelGGL(traverse_bre_kernel<16>, dim3((nwaves + TRAV_WPB - 1) / TRAV_WPB), dim3(64 * TRAV_WPB), 0, stream, a, items, itemOff, itemCount, queueHead, pairs, pairCnt, persist, units, unitCtl, unitCap); break;
+    case 64: if (own) GVPM_LAUNCH_TRAV(64, true); else GVPM_LAUNCH_TRAV(64, false); break;
+    case 32: if (own) GVPM_LAUNCH_TRAV(32, true); else GVPM_LAUNCH_TRAV(32, false); break;
+    default: if (own) GVPM_LAUNCH_TRAV(16, true); else GVPM_LAUNCH_TRAV(16, false); break;
   }
+#undef GVPM_LAUNCH_TRAV
 }
 
 template <bool FULLVIS, bool PF, bool HS = false>
