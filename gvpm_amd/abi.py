@@ -161,8 +161,36 @@ BSDF_DTYPE = np.dtype([("kind", np.int32), ("specular", np.float32, 3), ("expone
                        ("eta", np.float32, 3), ("k", np.float32, 3), ("reserved", np.float32, 2)])
 assert BSDF_DTYPE.itemsize == 64
 GVPM_BSDF_PHONG, GVPM_BSDF_ROUGHCONDUCTOR, GVPM_BSDF_WARD = 1, 2, 3
+GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC = 4, 5
+GVPM_RTRANS_KNOTS, GVPM_RTRANS_ENTRIES = 100, 7
+
 GVPM_WARD_WARD, GVPM_WARD_DUER, GVPM_WARD_BALANCED = 0, 1, 2
 GVPM_MICROFACET_BECKMANN, GVPM_MICROFACET_GGX = 0, 1
+
+
+def rtrans_entries(values):
+    """the 7 raw table entries that carry a rough-plastic head's transmittance slice (100 floats, then 12 zero words)"""
+    values = np.ascontiguousarray(values, np.float32)
+    assert values.shape == (GVPM_RTRANS_KNOTS,)
+    raw = np.zeros(GVPM_RTRANS_ENTRIES * 16, np.float32)
+    raw[:GVPM_RTRANS_KNOTS] = values
+    return raw.view(BSDF_DTYPE)
+
+
+def rtrans_of(table, head):
+    """the slice behind head entry `head` of a table"""
+    return np.ascontiguousarray(table[head + 1:head + 1 + GVPM_RTRANS_ENTRIES]).view(np.float32)[:GVPM_RTRANS_KNOTS]
+
+
+def plastic_entry(kind, specular, eta, fdr, weight, component, alpha=0.0, distribution=0, sample_visible=0, nonlinear=False):
+    """one GVPM_BSDF_ROUGHPLASTIC / GVPM_BSDF_PLASTIC head entry (include/gvpm_hip.h)"""
+    b = np.zeros(1, BSDF_DTYPE)
+    b["kind"], b["specular"], b["exponent"], b["specular_sampling_weight"] = kind, specular, alpha, weight
+    b["distribution"], b["sample_visible"] = distribution, sample_visible
+    b["eta"][0, :2] = eta, fdr
+    b["k"][0, :2] = component, 1.0 if nonlinear else 0.0
+    return b
+
 
 # compact camera-beam sets (include/gvpm_hip.h, "compact camera-beam sets")
 BEAM_SET_COMPACT_DTYPE = np.dtype([

@@ -2,6 +2,7 @@
 // Mirrors the driver logic of GPMIntegrator::photonMapPass / computeVolumeGradientPhotonBRE
 // (gvpm/gvpm.cpp:383-500, 988-1079) and scaleVolumeAPA (gvpm.cpp:181-215).
 #include "context.h"
+#include <cfloat>
 
 RcclApi g_rccl;
 
@@ -394,13 +395,44 @@ int gvpm_upload_bsdfs(gvpm_context *h, const gvpm_bsdf *table, uint32_t n) {
         return fail(h, GVPM_ERR_INVALID_ARG, "Ward: alpha >= 0.05 (both components) and a sampling weight in [0, 1]");
       if (b.sample_visible < GVPM_WARD_WARD || b.sample_visible > GVPM_WARD_BALANCED || b.distribution != 0)
         return fail(h, GVPM_ERR_UNSUPPORTED, "Ward: variant ward / ward-duer / balanced, both components");
+    } else if (b.kind == GVPM_BSDF_ROUGHPLASTIC || b.kind == GVPM_BSDF_PLASTIC) {
+      // (include/gvpm_hip.h: eta[0] = eta, eta[1] = Fdr, k[0] = the component met, k[1] = nonlinear)
+      const bool rough = b.kind == GVPM_BSDF_ROUGHPLASTIC;
+      if (rough && !(b.exponent >= 1e-4f)) return fail(h, GVPM_ERR_INVALID_ARG, "rough plastic: alpha >= 1e-4 (the reference clamps it)");
+      if (rough && b.distribution != GVPM_MICROFACET_BECKMANN && b.distribution != GVPM_MICROFACET_GGX)
+        return fail(h, GVPM_ERR_UNSUPPORTED, "rough plastic: Beckmann or GGX");
+      if (!(b.eta[0] >= 1.f && b.eta[0] <= FLT_MAX) || !(b.eta[1] >= 0.f && b.eta[1] < 1.f) ||
+          !(b.specular_sampling_weight >= 0.f && b.specular_sampling_weight <= 1.f))
+        return fail(h, GVPM_ERR_INVALID_ARG, "plastic: eta >= 1 and finite, Fdr in [0, 1), a sampling weight in [0, 1]");
+      if (rough ? !(b.k[0] == 0.f || b.k[0] == 1.f || b.k[0] == 2.f) : b.k[0] != 2.f)
+        return fail(h, GVPM_ERR_INVALID_ARG, "plastic: component 0 / 1 / 2 (rough plastic), 2 = the diffuse one (plastic)");
+      if (b.k[1] != 0.f && b.k[1] != 1.f) return fail(h, GVPM_ERR_INVALID_ARG, "plastic: nonlinear is 0 or 1");
+      if (rough) {
+        // the slice: GVPM_RTRANS_ENTRIES raw entries behind the head, copied as they are
+        if (n - i <= (uint32_t)GVPM_RTRANS_ENTRIES)
+          return fail(h, GVPM_ERR_INVALID_ARG, "rough plastic: the 7 entries of the transmittance slice are missing");
+        float raw[16 * GVPM_RTRANS_ENTRIES];
+        memcpy(raw, &table[i + 1], sizeof raw);
+        for (int j = 0; j < 16 * GVPM_RTRANS_ENTRIES; ++j) {
+          // (zero or a NORMAL float: a raw entry's first word must never read as a kind)
+          const bool okv = j < GVPM_RTRANS_KNOTS ? (raw[j] == 0.f || (raw[j] >= FLT_MIN && raw[j] <= 1.f)) : raw[j] == 0.f;
+          uint32_t bits;
+          memcpy(&bits, &raw[j], 4);
+          if (!okv || bits == 0x80000000u)
+            return fail(h, GVPM_ERR_INVALID_ARG, "rough plastic: slice values are finite, in [0, 1] and not subnormal; 12 zero words behind them");
+        }
+      }
     } else {
-      return fail(h, GVPM_ERR_UNSUPPORTED, "bsdf kind outside the device's closed set (Phong, rough conductor, Ward)");
+      return fail(h, GVPM_ERR_UNSUPPORTED, "bsdf kind outside the device's closed set (Phong, rough conductor, Ward, the plastics)");
     }
     rows[4 * i] = make_float4(kindBits, b.specular[0], b.specular[1], b.specular[2]);
     rows[4 * i + 1] = make_float4(b.exponent, b.specular_sampling_weight, distBits, visBits);
     rows[4 * i + 2] = make_float4(b.eta[0], b.eta[1], b.eta[2], b.k[0]);
     rows[4 * i + 3] = make_float4(b.k[1], b.k[2], 0.f, 0.f);
+    if (b.kind == GVPM_BSDF_ROUGHPLASTIC) {
+      memcpy(&rows[4 * (size_t)i + 4], &table[i + 1], GVPM_RTRANS_ENTRIES * sizeof(gvpm_bsdf));
+      i += GVPM_RTRANS_ENTRIES;
+    }
   }
   // once per scene: waits for whatever still reads the old table (as gvpm_upload_materials does)
   HIP_TRY(h, hipStreamSynchronize(h->stream));

@@ -466,6 +466,29 @@ __device__ __forceinline__ float fresnelConductor(float cI, float eta, float k) 
   const float Rp2 = Rs2 * fdiv(term3 - term4, term3 + term4);
   return 0.5f * (Rp2 + Rs2);
 }
+// fresnelDielectricExt for a cosine >= 0 and eta >= 1 (src/libcore/util.cpp:659-689): exactly 0 at eta == 1; no total internal
+// reflection from the rarer side
+__device__ __forceinline__ float fresnelDielectric(float cI, float eta) {
+  if (eta == 1.f) return 0.f;
+  const float ie = frcp(eta);
+  const float cT = fsqrt(fmaxf(1.f - (1.f - cI * cI) * (ie * ie), 0.f));
+  const float Rs = fdiv(cI - eta * cT, cI + eta * cT), Rp = fdiv(eta * cI - cT, eta * cI + cT);
+  return 0.5f * (Rs * Rs + Rp * Rp);
+}
+// RoughTransmittance::eval with eta and alpha fixed (src/bsdfs/rtrans.h:183-236): evalCubicInterp1D (libcore/spline.cpp:23-60)
+// of the 100 values `t` over cos^(1/4) in [0, 1] -- Catmull-Rom, one-sided differences at the ends, left knot
+// min(floor(x), 98) -- clamped to [0, 1].  c > 0 is the caller's test; a cosine that rounding left above 1 is looked up at 1.
+__device__ __forceinline__ float roughTransmittance(const float *__restrict__ t, float c) {
+  const float x = fsqrt(fsqrt(fminf(c, 1.f))) * (float)(GVPM_RTRANS_KNOTS - 1);
+  const int k = min((int)x, GVPM_RTRANS_KNOTS - 2);
+  const float f0 = t[k], f1 = t[k + 1];
+  const float fm = t[max(k - 1, 0)], f2 = t[min(k + 2, GVPM_RTRANS_KNOTS - 1)];
+  const float d0 = k > 0 ? 0.5f * (f1 - fm) : f1 - f0;
+  const float d1 = k + 2 < GVPM_RTRANS_KNOTS ? 0.5f * (f2 - f0) : f1 - f0;
+  const float u = x - (float)k, u2 = u * u, u3 = u2 * u;
+  const float r = (2.f * u3 - 3.f * u2 + 1.f) * f0 + (-2.f * u3 + 3.f * u2) * f1 + (u3 - 2.f * u2 + u) * d0 + (u3 - u2) * d1;
+  return fminf(fmaxf(r, 0.f), 1.f);
+}
 
 // A glossy surface parent (GVPM_PARENT_SURFACE_BSDF): BSDF::eval and BSDF::pdf * pdfComponent of the table entry the
 // record names, towards the new direction `wo` (shift_diffuse.cpp:25-41 with bRec.component = -1).  Phong, src/bsdfs/
@@ -542,6 +565,46 @@ __device__ __forceinline__ bool glossyParentEval(const GatherArgs &a, float inde
     f = mk3(fresnelConductor(wiH, b2.x, b2.w) * b0.y, fresnelConductor(wiH, b2.y, b3.x) * b0.z,
             fresnelConductor(wiH, b2.z, b3.y) * b0.w) * model;
     pdf = vis ? fdiv(D * G1i, 4.f * cosWi) : fdiv(D * cH, 4.f * fabsf(woH));
+    return true;
+  }
+  if (kind == GVPM_BSDF_ROUGHPLASTIC || kind == GVPM_BSDF_PLASTIC) {
+    // src/bsdfs/roughplastic.cpp:326-437,566-586 and the diffuse component of src/bsdfs/plastic.cpp:245-307,451-477
+    // (include/gvpm_hip.h): row 2 = {eta, Fdr, -, component met}, row 3 = {nonlinear, ...}; a rough-plastic head is followed by
+    // its transmittance slice, 100 contiguous floats (gvpm_upload_bsdfs checked that they are there)
+    const float4 b2 = a.bsdfs[4 * bi + 2], b3 = a.bsdfs[4 * bi + 3];
+    const float w = b1.y, eta = b2.x, Fdr = b2.y;
+    const int comp = (int)b2.w;  // 0 both, 1 the glossy component alone, 2 the diffuse one alone
+    float Ti, To, spec = 0.f, pdfM = 0.f;
+    if (kind == GVPM_BSDF_ROUGHPLASTIC) {
+      const float *slice = reinterpret_cast<const float *>(a.bsdfs + 4 * (bi + 1));
+      Ti = roughTransmittance(slice, cosWi);
+      To = roughTransmittance(slice, cosWo);
+      const float alpha = b1.x;
+      const int ggx = __float_as_int(b1.z) == GVPM_MICROFACET_GGX, vis = __float_as_int(b1.w) != 0;
+      f3 H = wi + wo;
+      H = H * frsq(dot(H, H));
+      const float cH = dot(H, n), wiH = dot(wi, H), woH = dot(wo, H);
+      const float D = microfacetD(ggx, alpha, cH);
+      if (D != 0.f && comp != 2) {
+        const float G1i = microfacetG1(ggx, alpha, cosWi, wiH), G1o = microfacetG1(ggx, alpha, cosWo, woH);
+        spec = fresnelDielectric(wiH, eta) * fdiv(D * G1i * G1o, 4.f * cosWi);
+        pdfM = vis ? fdiv(D * G1i, 4.f * cosWi) : fdiv(D * cH, 4.f * fabsf(woH));
+      }
+    } else {
+      Ti = 1.f - fresnelDielectric(cosWi, eta);
+      To = 1.f - fresnelDielectric(cosWo, eta);
+    }
+    // the probability of the glossy component: 0 / 0 (T = 0 with w = 0, T = 1 with w = 1) is NaN in the reference -- a failed shift
+    const float p = 1.f - Ti, den = p * w + (1.f - p) * (1.f - w);
+    if (!(den > 0.f)) return false;
+    const float pS = fdiv(p * w, den);
+    const float dOn = comp == 1 ? 0.f : 1.f;
+    const bool nl = b3.x != 0.f;  // kd / (1 - kd Fdr) per channel, else kd / (1 - Fdr)
+    const f3 kdp = mk3(fdiv(kd.x, 1.f - (nl ? kd.x : 1.f) * Fdr), fdiv(kd.y, 1.f - (nl ? kd.y : 1.f) * Fdr),
+                       fdiv(kd.z, 1.f - (nl ? kd.z : 1.f) * Fdr));
+    const float ie = frcp(eta);
+    f = mk3(b0.y, b0.z, b0.w) * spec + kdp * (INV_PI_F * cosWo * Ti * To * (ie * ie) * dOn);
+    pdf = pS * pdfM + (1.f - pS) * (INV_PI_F * cosWo * dOn);
     return true;
   }
   return false;

@@ -451,7 +451,8 @@ class Context:
         self._check(lib().gvpm_upload_camera_beams_packed(self._h, packed.ctypes.data if n else None, n))
 
     def upload_bsdfs(self, table):
-        """table: numpy array of abi.BSDF_DTYPE (the scene's glossy surfaces)"""
+        """table: numpy array of abi.BSDF_DTYPE (the scene's glossy surfaces); a GVPM_BSDF_ROUGHPLASTIC entry is followed by the
+        7 raw entries of its transmittance slice (abi.rtrans_entries).  A refused table leaves the previous one in force."""
         table = np.ascontiguousarray(table, abi.BSDF_DTYPE)
         self._check(lib().gvpm_upload_bsdfs(self._h, table.ctypes.data if table.size else None, table.size))
 

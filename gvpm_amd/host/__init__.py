@@ -45,6 +45,11 @@ def lib():
         L.gvpm_synth_stream_check.restype = C.c_uint64
         L.gvpm_synth_stream_check.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p]
         L.gvpm_synth_bsdfs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.gvpm_synth_rtrans_materials.restype = C.c_uint32
+        L.gvpm_synth_rtrans_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.gvpm_synth_set_rtrans.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float]
+        L.gvpm_synth_sample_plastic.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
         L.gvpm_synth_sensor.argtypes = [C.c_void_p, C.POINTER(abi.Sensor)]
         L.gvpm_synth_jitter.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
         _LIB = L
@@ -94,6 +99,38 @@ class SynthScene:
             lib().gvpm_synth_bsdfs(self._h, out.ctypes.data, n)
         return out
 
+    def rtrans_materials(self):
+        """the scene's rough-plastic materials, in table order: [(material index, "beckmann" | "ggx", alpha, eta)] -- each needs
+        its transmittance slice (set_rtrans) before photons or beams are shot"""
+        n = lib().gvpm_synth_rtrans_materials(self._h, None, None, None, None, 0)
+        mats, dist = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        alpha, eta = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        if n:
+            lib().gvpm_synth_rtrans_materials(self._h, mats.ctypes.data, dist.ctypes.data, alpha.ctypes.data, eta.ctypes.data, n)
+        return [(int(mats[i]), "ggx" if dist[i] == abi.GVPM_MICROFACET_GGX else "beckmann", float(alpha[i]), float(eta[i]))
+                for i in range(n)]
+
+    def set_rtrans(self, mat, values, fdr):
+        """the rough transmittance of material `mat` at its eta and alpha: 100 values in [0, 1] over cos^(1/4) (the slice the
+        reference reduces its data files to) and Fdr = 1 - the internal diffuse transmittance.  Data derived from the
+        reference's files: it comes from the caller (tests: tests/golden/rtrans_slices.npz)."""
+        values = np.ascontiguousarray(values, np.float32)
+        rc = lib().gvpm_synth_set_rtrans(self._h, mat, values.ctypes.data, values.size, fdr)
+        if rc != 0:
+            raise ValueError(f"set_rtrans({mat}): not a rough-plastic material, or values outside [0, 1] / not {abi.GVPM_RTRANS_KNOTS} of them")
+
+    def sample_plastic(self, mat, n, wi, u1, u2):
+        """one bounce off plastic material `mat` as the light-path walk takes it: (wo, weight, pdf, component) or None when the
+        sample is lost; component -1: both were in play, 0: the glossy / Dirac one alone, 1: the diffuse one alone"""
+        n, wi = np.ascontiguousarray(n, np.float64), np.ascontiguousarray(wi, np.float64)
+        wo, weight = np.zeros(3), np.zeros(3)
+        pdf, comp = C.c_double(0), C.c_int(0)
+        rc = lib().gvpm_synth_sample_plastic(self._h, mat, n.ctypes.data, wi.ctypes.data, u1, u2, wo.ctypes.data, weight.ctypes.data,
+                                             C.addressof(pdf), C.addressof(comp))
+        if rc < 0:
+            raise ValueError(f"sample_plastic({mat}): not a plastic material, or its slice is missing")
+        return (wo, weight, pdf.value, comp.value) if rc == 1 else None
+
     def sensor(self):
         """the scene's pinhole sensor (gvpm_sensor) the compact beam sets are decoded with"""
         s = abi.Sensor()
@@ -120,7 +157,9 @@ class SynthScene:
         """-> (abi.Photons, nb_paths)"""
         soa = abi.PhotonSoA()
         nb = C.c_uint64(0)
-        lib().gvpm_synth_shoot(self._h, iteration, capacity, C.byref(soa), C.byref(nb))
+        n = lib().gvpm_synth_shoot(self._h, iteration, capacity, C.byref(soa), C.byref(nb))
+        if n == 2 ** 64 - 1:
+            raise RuntimeError("a rough-plastic material has no transmittance slice: set_rtrans first")
         return abi.Photons.from_soa(soa), int(nb.value)
 
     def shoot_beams(self, iteration, capacity):
@@ -129,6 +168,8 @@ class SynthScene:
         nb = C.c_uint64(0)
         ptr = C.c_void_p()
         n = lib().gvpm_synth_shoot_beams(self._h, iteration, capacity, C.byref(soa), C.byref(ptr), C.byref(nb))
+        if n == 2 ** 64 - 1:
+            raise RuntimeError("a rough-plastic material has no transmittance slice: set_rtrans first")
         beams = abi.Photons.from_soa(soa)
         end_n = (np.array((C.c_float * (3 * n)).from_address(ptr.value), np.float32).reshape(n, 3).copy()
                  if n else np.zeros((0, 3), np.float32))

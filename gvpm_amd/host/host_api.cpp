@@ -98,6 +98,7 @@ int gvpm_synth_triangles(gvpm_synth *s, gvpm_triangles *out) {
 uint64_t gvpm_synth_shoot(gvpm_synth *s, int it, uint64_t capacity, gvpm_photon_soa *out,
                           uint64_t *nb_paths) {
   if (!s || !out) return 0;
+  if (!s->scene.rtransComplete()) return UINT64_MAX;
   uint64_t np = gvpm::shootPhotons(s->scene, it, capacity, s->photons);
   if (nb_paths) *nb_paths = np;
   s->photons.view(*out);
@@ -107,6 +108,7 @@ uint64_t gvpm_synth_shoot(gvpm_synth *s, int it, uint64_t capacity, gvpm_photon_
 uint64_t gvpm_synth_shoot_beams(gvpm_synth *s, int it, uint64_t capacity, gvpm_photon_soa *out,
                                 const float **end_n, uint64_t *nb_paths) {
   if (!s || !out || !end_n) return 0;
+  if (!s->scene.rtransComplete()) return UINT64_MAX;
   uint64_t np = gvpm::shootBeams(s->scene, it, capacity, s->photons, s->endN);
   if (nb_paths) *nb_paths = np;
   s->photons.view(*out);
@@ -137,11 +139,73 @@ uint64_t gvpm_synth_beams_interleaved(gvpm_synth *s, int it, int tile_mod, int t
   return s->rays.size() / 5;
 }
 
+uint32_t gvpm_synth_rtrans_materials(const gvpm_synth *s, int32_t *mats, int32_t *distribution, float *alpha, float *eta, uint32_t cap) {
+  if (!s) return 0;
+  uint32_t n = 0;
+  for (size_t i = 0; i < s->scene.mats.size(); ++i) {
+    const auto &m = s->scene.mats[i];
+    if (m.kind != gvpm::MAT_ROUGHPLASTIC) continue;
+    if (n < cap) {
+      if (mats) mats[n] = (int32_t)i;
+      if (distribution) distribution[n] = m.distribution;
+      if (alpha) alpha[n] = (float)m.exponent;
+      if (eta) eta[n] = (float)m.coatEta;
+    }
+    ++n;
+  }
+  return n;
+}
+
+int gvpm_synth_set_rtrans(gvpm_synth *s, int mat, const float *values, int n, float fdr) {
+  if (!s) return GVPM_ERR_INVALID_ARG;
+  return s->scene.setRtrans(mat, values, n, fdr) ? GVPM_OK : GVPM_ERR_INVALID_ARG;
+}
+
+int gvpm_synth_sample_plastic(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
+                              double *weight, double *pdf, int *component) {
+  using namespace gvpm;
+  if (!s || !n || !wi || !wo || !weight || !pdf || !component || mat < 0 || mat >= (int)s->scene.mats.size()) return GVPM_ERR_INVALID_ARG;
+  const SynthMat &pm = s->scene.mats[mat];
+  if ((pm.kind != MAT_ROUGHPLASTIC && pm.kind != MAT_PLASTIC) || (pm.kind == MAT_ROUGHPLASTIC && !pm.rtrans)) return GVPM_ERR_INVALID_ARG;
+  V3 o, w;
+  uint32_t comp = 0;
+  int compSel = -1;
+  bool solidAngle = true;
+  if (!samplePlastic(pm, V3(n[0], n[1], n[2]), V3(wi[0], wi[1], wi[2]), u1, u2, o, w, *pdf, comp, compSel, solidAngle)) return 0;
+  wo[0] = o.x; wo[1] = o.y; wo[2] = o.z;
+  weight[0] = w.x; weight[1] = w.y; weight[2] = w.z;
+  *component = compSel;
+  return 1;
+}
+
 uint32_t gvpm_synth_bsdfs(const gvpm_synth *s, gvpm_bsdf *out, uint32_t cap) {
   if (!s) return 0;
   uint32_t n = 0;
   for (const auto &m : s->scene.mats) {
     const int entries = gvpm::bsdfEntries(m.kind, m.exponent);
+    if (m.kind == gvpm::MAT_ROUGHPLASTIC || m.kind == gvpm::MAT_PLASTIC) {
+      // a head per component met (below alpha 0.05: glossy alone, diffuse alone); a rough head is followed by its slice
+      const int stride = m.kind == gvpm::MAT_ROUGHPLASTIC ? 1 + GVPM_RTRANS_ENTRIES : 1;
+      for (int c = 0; c < entries; ++c) {
+        if (out && (uint32_t)(m.bsdf + (c + 1) * stride) <= cap) {
+          gvpm_bsdf *b = &out[m.bsdf + c * stride];
+          memset(b, 0, stride * sizeof(gvpm_bsdf));
+          b->kind = m.kind == gvpm::MAT_ROUGHPLASTIC ? GVPM_BSDF_ROUGHPLASTIC : GVPM_BSDF_PLASTIC;
+          b->specular[0] = (float)m.spec.x; b->specular[1] = (float)m.spec.y; b->specular[2] = (float)m.spec.z;
+          b->exponent = (float)m.exponent;
+          b->specular_sampling_weight = (float)m.specWeight;
+          b->distribution = m.kind == gvpm::MAT_ROUGHPLASTIC ? m.distribution : 0;
+          b->sample_visible = 0;  // (the host walk samples all normals, synth_core.h)
+          b->eta[0] = (float)m.coatEta;
+          b->eta[1] = (float)m.fdr;
+          b->k[0] = m.kind == gvpm::MAT_PLASTIC ? 2.f : (entries == 2 ? (float)(c + 1) : 0.f);
+          b->k[1] = (float)m.nonlinear;
+          if (stride > 1 && m.rtrans) memcpy(b + 1, m.rtrans, GVPM_RTRANS_KNOTS * sizeof(float));
+        }
+        n += stride;
+      }
+      continue;
+    }
     for (int c = 0; c < entries; ++c) {
       if (out && (uint32_t)(m.bsdf + c) < cap) {
         gvpm_bsdf &b = out[m.bsdf + c];

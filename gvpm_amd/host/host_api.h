@@ -19,6 +19,8 @@ int gvpm_synth_triangles(gvpm_synth *s, gvpm_triangles *out);
  * *out points into buffers owned by `s` (valid until the next shoot) */
 uint64_t gvpm_synth_shoot(gvpm_synth *s, int it, uint64_t capacity, gvpm_photon_soa *out,
                           uint64_t *nb_paths);
+/* (both shoot calls return UINT64_MAX, and store nothing, when a rough-plastic material of the scene has no transmittance
+ * slice yet: gvpm_synth_set_rtrans) */
 /* photon beams of iteration `it` (see gvpm_upload_beams); *end_n: 3 floats per beam */
 uint64_t gvpm_synth_shoot_beams(gvpm_synth *s, int it, uint64_t capacity, gvpm_photon_soa *out,
                                 const float **end_n, uint64_t *nb_paths);
@@ -29,7 +31,20 @@ uint64_t gvpm_synth_planes(gvpm_synth *s, int it, const float **w1, const float 
 /* camera beam sets of the pixel rectangle; returns the number of sets */
 uint64_t gvpm_synth_beams(gvpm_synth *s, int it, int x0, int y0, int x1, int y1,
                           const gvpm_camera_ray **out);
-/* the BSDF table of the scene's glossy (Phong) walls, in the order the photons' parent_g name them (gvpm_upload_bsdfs);
+/* rough-plastic materials (scenes cbox_roughplastic*): the material indices, in table order (at most cap written; returns
+ * their number), and the setter of a material's transmittance slice -- n = GVPM_RTRANS_KNOTS values in [0, 1] over
+ * cos^(1/4) -- and Fdr (include/gvpm_hip.h, GVPM_BSDF_ROUGHPLASTIC).  The slice is derived from the reference renderer's data
+ * files and comes from the caller.  GVPM_ERR_INVALID_ARG: not such a material, n or a value out of range. */
+uint32_t gvpm_synth_rtrans_materials(const gvpm_synth *s, int32_t *mats, int32_t *distribution, float *alpha, float *eta, uint32_t cap);
+int gvpm_synth_set_rtrans(gvpm_synth *s, int mat, const float *values, int n, float fdr);
+/* A TEST HOOK, not something a renderer needs: it lets the chi-square tests drive the walk's own sampling code instead of a
+ * copy of it.  One bounce off plastic material `mat` exactly as the light-path walk takes it (synth_core.h samplePlastic): unit normal n,
+ * unit wi (towards the previous vertex), the vertex's two random numbers.  Returns 1 and wo, weight (eval / pdf), pdf
+ * (solid angle; discrete for the Dirac component, *component = 0 then) and the sampled component (-1: both were in play),
+ * 0 when the sample is lost, GVPM_ERR_INVALID_ARG for another kind of material or a missing slice. */
+int gvpm_synth_sample_plastic(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
+                              double *weight, double *pdf, int *component);
+/* the BSDF table of the scene's glossy walls (a rough-plastic head is followed by the raw entries of its slice), in the order the photons' parent_g name them (gvpm_upload_bsdfs);
  * returns the number of entries (at most cap are written) */
 uint32_t gvpm_synth_bsdfs(const gvpm_synth *s, gvpm_bsdf *out, uint32_t cap);
 /* self-check of the streaming flattening the device generator uses (StreamPath, synth_core.h) against flattenPath /

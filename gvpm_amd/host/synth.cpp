@@ -31,6 +31,30 @@ SceneView SynthScene::view() const {
   return v;
 }
 
+// copies re-point their rough-plastic materials at their own copy of the slices
+void SynthScene::rebindRtrans() {
+  for (size_t i = 0; i < mats.size(); ++i)
+    mats[i].rtrans = (i < rtransStore.size() && !rtransStore[i].empty()) ? rtransStore[i].data() : nullptr;
+}
+
+bool SynthScene::setRtrans(int mat, const float *values, int n, double fdr) {
+  if (mat < 0 || mat >= (int)mats.size() || mats[mat].kind != MAT_ROUGHPLASTIC || !values || n != GVPM_RTRANS_KNOTS) return false;
+  if (!(fdr >= 0.0 && fdr < 1.0)) return false;
+  for (int i = 0; i < n; ++i)
+    if (!(values[i] >= 0.f && values[i] <= 1.f)) return false;
+  rtransStore.resize(mats.size());
+  rtransStore[mat].assign(values, values + n);
+  mats[mat].rtrans = rtransStore[mat].data();
+  mats[mat].fdr = fdr;
+  return true;
+}
+
+bool SynthScene::rtransComplete() const {
+  for (const auto &m : mats)
+    if (m.kind == MAT_ROUGHPLASTIC && !m.rtrans) return false;
+  return true;
+}
+
 double SynthScene::bsphereRadius() const {
   // AABB::getBSphere(): centre = box centre, radius = |max - centre|
   V3 c = (bmin + bmax) * 0.5;
@@ -216,6 +240,46 @@ bool makeScene(const std::string &fullName, int width, int height, uint32_t seed
     };
     const int mFloor = conductor(V3(0.2004, 0.9240, 1.1022), V3(3.9129, 2.4528, 2.1421), 0.3, GVPM_MICROFACET_BECKMANN);
     const int mBack = conductor(V3(1.6574, 0.8803, 0.5212), V3(9.2238, 6.2695, 4.8370), 0.2, GVPM_MICROFACET_GGX);
+    addBoxRoom(s, mFloor, 0, mBack, 1, 2, 3);
+    if (rot) addCornellBlocks(s, 0, mBack);
+    setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);
+    setMedium(s, 0.5, 0.5, 0.0);
+  } else if (name == "cbox_roughplastic" || name == "cbox_roughplastic1" || name == "cbox_plastic") {
+    // S-cbox with PLASTIC walls (row f4): floor and back wall a dielectric coating (eta 1.5) over a diffuse base --
+    // src/bsdfs/roughplastic.cpp (floor Beckmann alpha 0.1, back wall GGX alpha 0.3; `1`: 0.03 / 0.04, below 0.05, so one
+    // component per bounce) or src/bsdfs/plastic.cpp (smooth).  The rough kinds need their transmittance slice before the
+    // first walk (SynthScene::setRtrans); Fdr comes with it, the smooth plastic's m_fdrInt is closed-form.
+    const bool smooth = name == "cbox_plastic", one = name == "cbox_roughplastic1";
+    auto plastic = [&](V3 kd, V3 ks, double alpha, int distribution, bool nonlinear) {
+      auto lum = [](V3 c) { return 0.212671 * c.x + 0.715160 * c.y + 0.072169 * c.z; };  // Spectrum::getLuminance, RGB
+      SynthMat m{smooth ? MAT_PLASTIC : MAT_ROUGHPLASTIC, kd, ks, smooth ? 0.0 : alpha, lum(ks) / (lum(kd) + lum(ks)), 0};
+      const double eta = 1.5;
+      // fresnelDiffuseReflectance(1 / eta, false) (util.cpp:822-880: the integral of the reflectance seen from the denser side
+      // over xi = cos^2 in [0, 1]), what plastic.cpp:194 keeps as m_fdrInt -- midpoint rule over the cosine
+      double fdrInt = 0.0;
+      const int steps = 200000;
+      for (int q = 0; smooth && q < steps; ++q) {
+        const double mu = (q + 0.5) / steps, s2 = (1 - mu * mu) * eta * eta;
+        double F = 1.0;  // total internal reflection
+        if (s2 < 1) {
+          const double ct = std::sqrt(1 - s2), rs = (eta * mu - ct) / (eta * mu + ct), rp = (mu - eta * ct) / (mu + eta * ct);
+          F = 0.5 * (rs * rs + rp * rp);
+        }
+        fdrInt += F * 2 * mu / steps;
+      }
+      m.coatEta = eta;
+      m.fdr = fdrInt;  // (rough: 0 until setRtrans brings it with the slice)
+      m.nonlinear = nonlinear ? 1 : 0;
+      m.distribution = distribution;
+      m.bsdf = 0;
+      for (const auto &q : s.mats) m.bsdf += bsdfSlots(q.kind, q.exponent);
+      s.mats.push_back(m);
+      return (int)s.mats.size() - 1;
+    };
+    // (a coated surface is darker than its base: kd' T T / eta^2 is about 0.36 kd / (1 - 0.6 [kd]); bright bases keep as many
+    // photons behind these walls as behind the Phong ones)
+    const int mFloor = plastic(V3(0.7, 0.7, 0.7), V3(1.0, 1.0, 0.9), one ? 0.03 : 0.1, GVPM_MICROFACET_BECKMANN, false);
+    const int mBack = plastic(V3(0.6, 0.7, 0.9), V3(0.9, 0.9, 0.9), one ? 0.04 : 0.3, GVPM_MICROFACET_GGX, true);
     addBoxRoom(s, mFloor, 0, mBack, 1, 2, 3);
     if (rot) addCornellBlocks(s, 0, mBack);
     setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);

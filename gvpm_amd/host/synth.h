@@ -22,7 +22,8 @@
 
 namespace gvpm {
 
-struct SynthScene {
+// (the data of a scene apart, so that SynthScene's copies are memberwise copies plus rebindRtrans)
+struct SynthSceneData {
   std::string name;
   std::vector<SynthTri> tris;
   std::vector<SynthMat> mats;
@@ -46,11 +47,32 @@ struct SynthScene {
   // `_rot` scenes: the rotation every point / direction of the scene description goes through (rows of R)
   bool rotated = false;
   V3 rot[3] = {V3(1, 0, 0), V3(0, 1, 0), V3(0, 0, 1)};
+  // rough plastic: per material, its transmittance slice (empty: none) -- SynthMat::rtrans points in here
+  std::vector<std::vector<float>> rtransStore;
+};
+
+struct SynthScene : SynthSceneData {
   V3 toWorld(V3 p) const;
 
   double bsphereRadius() const;
   SceneView view() const;  // what the generators (host or device) read
   void addQuad(V3 a, V3 b, V3 c, V3 d, int mat);  // a,b,c,d counter-clockwise seen from the front
+
+  // rough plastic: the transmittance slice (GVPM_RTRANS_KNOTS values in [0, 1]) and Fdr of material `mat`, from the caller --
+  // data derived from the reference's tables, which this library does not carry.  False: not a rough-plastic material or
+  // values out of range.  The materials point into rtransStore: a copy of a scene re-points its own (rebindRtrans).
+  bool setRtrans(int mat, const float *values, int n, double fdr);
+  bool rtransComplete() const;  // every rough-plastic material has its slice
+  void rebindRtrans();
+  SynthScene() = default;
+  SynthScene(const SynthScene &o) : SynthSceneData(o) { rebindRtrans(); }
+  SynthScene &operator=(const SynthScene &o) {
+    SynthSceneData::operator=(o);
+    rebindRtrans();
+    return *this;
+  }
+  SynthScene(SynthScene &&) = default;  // (moved vectors keep their buffers: the pointers stay good)
+  SynthScene &operator=(SynthScene &&) = default;
 };
 
 bool makeScene(const std::string &name, int width, int height, uint32_t seed, SynthScene &out);

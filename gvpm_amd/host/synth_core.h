@@ -24,6 +24,11 @@ namespace gvpm {
 // (sampleVisible = false: MicrofacetDistribution::sampleAll) -- the table's second kind
 // MAT_WARD (round 5): src/bsdfs/ward.cpp, isotropic (alphaU == alphaV = `exponent`), roughness >= 0.05: both components sampled
 // together; `distribution` holds the model variant (GVPM_WARD_*)
+// MAT_ROUGHPLASTIC: src/bsdfs/roughplastic.cpp, isotropic Beckmann / GGX, sampled without visible normals; `exponent` = alpha,
+// `coatEta`, `fdr`, `nonlinear`, `rtrans` = its 100-value transmittance slice (from the caller: the slice is data
+// derived from the reference's tables and does not live in this library).  Below roughness 0.05 one component per bounce.
+// MAT_PLASTIC: src/bsdfs/plastic.cpp, always one component per bounce: the Dirac reflection (a specular vertex, as a mirror's)
+// or the diffuse base (the table's GVPM_BSDF_PLASTIC entry); `fdr` = the closed-form m_fdrInt
 // The glossy kinds are sampled by the HOST generators only: the device generator's closed set is Lambertian / index-matched /
 // mirror (gvpm_devgen_create refuses the others), and their fp64 pow / atan / log chains cost the device walk a third of its
 // time in registers alone when they were merely compiled in.
@@ -32,12 +37,21 @@ namespace gvpm {
 #else
 #define GVPM_SYNTH_GLOSSY 1
 #endif
-enum MatKind { MAT_LAMBERT = 0, MAT_NULL = 1, MAT_MIRROR = 2, MAT_PHONG = 3, MAT_ROUGHCONDUCTOR = 4, MAT_WARD = 5 };
+enum MatKind { MAT_LAMBERT = 0, MAT_NULL = 1, MAT_MIRROR = 2, MAT_PHONG = 3, MAT_ROUGHCONDUCTOR = 4, MAT_WARD = 5, MAT_ROUGHPLASTIC = 6,
+               MAT_PLASTIC = 7 };
 // table entries of a glossy material: PathVertex::sampleNext picks ONE component of a Phong surface below roughness 0.05
 // (vertex.cpp:160-165, Phong::getRoughness = sqrt(2 / (2 + exponent)), phong.cpp:293-300): an entry per component then
 GVPM_HD inline bool phongOneComponent(double exponent) { return sqrt(2.0 / (2.0 + exponent)) < 0.05; }
+// (rough plastic: RoughPlastic::sampleComponent, roughplastic.cpp:532-539 -- alpha against the same constant; smooth plastic:
+// its diffuse component alone, the Dirac one is a specular vertex)
 GVPM_HD inline int bsdfEntries(int kind, double exponent) {
+  if (kind == MAT_ROUGHPLASTIC) return exponent < 0.05 ? 2 : 1;
+  if (kind == MAT_PLASTIC) return 1;
   return kind == MAT_PHONG ? (phongOneComponent(exponent) ? 2 : 1) : ((kind == MAT_ROUGHCONDUCTOR || kind == MAT_WARD) ? 1 : 0);
+}
+// table SLOTS of a material: a rough-plastic entry is a head followed by the raw entries of its slice (include/gvpm_hip.h)
+GVPM_HD inline int bsdfSlots(int kind, double exponent) {
+  return bsdfEntries(kind, exponent) * (kind == MAT_ROUGHPLASTIC ? 1 + GVPM_RTRANS_ENTRIES : 1);
 }
 
 struct SynthTri {
@@ -55,6 +69,11 @@ struct SynthMat {
   // rough conductor: spec = specular reflectance, exponent = alpha
   V3 eta = V3(0.0), k = V3(0.0);
   int distribution = 0;  // GVPM_MICROFACET_*
+  // the plastics: relative index of the coating, Fdr (rough: with its slice; smooth: m_fdrInt), m_nonlinear
+  double coatEta = 0.0, fdr = 0.0;
+  int nonlinear = 0;
+  // rough plastic: the transmittance slice, GVPM_RTRANS_KNOTS values in host memory owned by the SynthScene (null: not set yet)
+  const float *rtrans = nullptr;
 };
 
 // what the generators read of a scene (SynthScene::view(); the device gets the arrays in HBM)
@@ -116,6 +135,25 @@ GVPM_HD inline double conductorFresnel(double cI, double eta, double k) {
   const double Rs2 = (term1 - term2) / (term1 + term2);
   const double term3 = a2pb2 * c2 + s4, term4 = term2 * s2;
   return 0.5 * (Rs2 * (term3 - term4) / (term3 + term4) + Rs2);
+}
+// fresnelDielectricExt for a cosine >= 0 from outside a medium of relative index eta >= 1 (util.cpp:659-689)
+GVPM_HD inline double dielectricFresnel(double cI, double eta) {
+  if (eta == 1.0) return 0.0;
+  const double cT = std::sqrt(std::fmax(0.0, 1 - (1 - cI * cI) / (eta * eta)));
+  const double Rs = (cI - eta * cT) / (cI + eta * cT), Rp = (eta * cI - cT) / (eta * cI + cT);
+  return 0.5 * (Rs * Rs + Rp * Rp);
+}
+// RoughTransmittance::eval with eta and alpha fixed (rtrans.h:183-236 over evalCubicInterp1D, spline.cpp:23-60), clamped
+GVPM_HD inline double roughTransmittanceEval(const float *t, double c) {
+  const int m = GVPM_RTRANS_KNOTS;
+  const double x = std::sqrt(std::sqrt(std::fmin(std::fmax(c, 0.0), 1.0))) * (m - 1);
+  int k = (int)x;
+  if (k > m - 2) k = m - 2;
+  const double f0 = t[k], f1 = t[k + 1];
+  const double d0 = k > 0 ? 0.5 * (f1 - t[k - 1]) : f1 - f0, d1 = k + 2 < m ? 0.5 * (t[k + 2] - f0) : f1 - f0;
+  const double u = x - k, u2 = u * u, u3 = u2 * u;
+  const double r = (2 * u3 - 3 * u2 + 1) * f0 + (-2 * u3 + 3 * u2) * f1 + (u3 - 2 * u2 + u) * d0 + (u3 - u2) * d1;
+  return std::fmin(1.0, std::fmax(0.0, r));
 }
 
 // ------------------------------------------------------------------ scenes --
@@ -235,6 +273,122 @@ GVPM_HD inline double hgEval(double g, double cosWiWo) {
   double temp = 1.0 + g * g + 2.0 * g * cosWiWo;
   return kInvFourPi * (1 - g * g) / (temp * std::sqrt(temp));
 }
+
+#if GVPM_SYNTH_GLOSSY
+// One bounce off a plastic surface as PathVertex::sampleNext does it (vertex.cpp:160-173): component selection, BSDF::sample
+// with bRec.component, then weight /= pdfComponent, pdf *= pdfComponent.  (a, b): the vertex's two random numbers (sample.x,
+// sample.y).  False: the sample is lost (the walk ends).  solidAngle = false: a Dirac bounce, pdf in the discrete measure.
+inline bool samplePlastic(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp,
+                          int &compSel, bool &solidAngle) {
+  if (pm.kind == MAT_ROUGHPLASTIC) {
+    // PathVertex::sampleNext (vertex.cpp:160-173) over RoughPlastic (roughplastic.cpp): below alpha 0.05 sampleComponent
+    // (:532-564) picks ONE component with probability pS / 1 - pS and rescales sample.y AS WRITTEN there (the glossy branch
+    // MULTIPLIES by pS); then sample() (:439-501) with bRec.component: with both components sample.y picks the lobe; the
+    // half vector comes from MicrofacetDistribution::sampleAll (sampleVisible = false) as for the rough conductor; weight =
+    // eval / pdf of what bRec.component selects, then weight /= pdfComponent, pdf *= pdfComponent.
+    if (!pm.rtrans) return false;  // (shootPhotons / shootBeams refuse such a scene before any walk)
+    const double alpha = pm.exponent, alphaSqr = alpha * alpha, eta = pm.coatEta, Fdr = pm.fdr, sw = pm.specWeight;
+    const double cosWi = dot(n, wi);
+    const double Ti = roughTransmittanceEval(pm.rtrans, cosWi), pr = 1 - Ti;
+    const double pS = pr * sw / (pr * sw + (1 - pr) * (1 - sw));
+    double sy = b;
+    compSel = -1;
+    double pdfComp = 1.0;
+    if (alpha < 0.05) {
+      if (sy < pS) {
+        compSel = 0;
+        pdfComp = pS;
+        sy *= pS;
+      } else {
+        compSel = 1;
+        pdfComp = 1 - pS;
+        sy = (sy - pS) / (1 - pS);
+      }
+    }
+    const bool hasSpecular = compSel != 1, hasDiffuse = compSel != 0;
+    bool choseSpecular = hasSpecular;
+    if (hasSpecular && hasDiffuse) {
+      if (sy < pS) {
+        sy /= pS;
+      } else {
+        sy = (sy - pS) / (1 - pS);
+        choseSpecular = false;
+      }
+    }
+    if (choseSpecular) {
+      double tanThetaMSqr;
+      if (pm.distribution == GVPM_MICROFACET_GGX) tanThetaMSqr = alphaSqr * a / (1.0 - a);
+      else tanThetaMSqr = alphaSqr * -std::log(1.0 - a);
+      const double cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
+      const double sinThetaM = std::sqrt(std::fmax(0.0, 1 - cosThetaM * cosThetaM)), phi = 2.0 * kPi * sy;
+      const V3 m = toWorld(n, V3(sinThetaM * std::cos(phi), sinThetaM * std::sin(phi), cosThetaM));
+      wo = m * (2.0 * dot(wi, m)) - wi;
+      comp = 0x00008u;  // EGlossyReflection
+    } else {
+      wo = toWorld(n, cosineHemisphere(a, sy));
+      comp = GVPM_BSDF_DIFFUSE_REFLECTION;
+    }
+    const double cosWo = dot(n, wo);
+    if (cosWo <= 0) return false;
+    const V3 H = normalize(wi + wo);
+    const double cH = dot(n, H), wiH = dot(wi, H), woH = dot(wo, H);
+    const double D = hasSpecular ? conductorD(pm.distribution, alpha, cH) : 0.0;
+    const double probSpec = (hasSpecular && hasDiffuse) ? pS : 1.0, probDiff = (hasSpecular && hasDiffuse) ? 1 - pS : 1.0;
+    double pdfW = 0.0;
+    if (hasSpecular && D > 0) pdfW = D * cH / (4.0 * woH) * probSpec;
+    if (hasDiffuse) pdfW += probDiff * cosWo * kInvPi;
+    if (!(pdfW > 0)) return false;
+    V3 f(0.0);
+    if (hasSpecular && D > 0) {
+      const double G = conductorG1(pm.distribution, alpha, cosWi, wiH) * conductorG1(pm.distribution, alpha, cosWo, woH);
+      f = pm.spec * (dielectricFresnel(wiH, eta) * D * G / (4.0 * cosWi));
+    }
+    if (hasDiffuse) {
+      const double To = roughTransmittanceEval(pm.rtrans, cosWo), nl = pm.nonlinear;
+      const V3 kd = pm.albedo;
+      const V3 kdp(kd.x / (1 - (nl != 0 ? kd.x : 1.0) * Fdr), kd.y / (1 - (nl != 0 ? kd.y : 1.0) * Fdr), kd.z / (1 - (nl != 0 ? kd.z : 1.0) * Fdr));
+      f = f + kdp * (kInvPi * cosWo * Ti * To / (eta * eta));
+    }
+    weight = f * (1.0 / pdfW);
+    if (compSel != -1) {
+      weight = weight * (1.0 / pdfComp);
+      pdfW *= pdfComp;
+    }
+    pdf = pdfW;
+    if (maxc(weight) <= 0) return false;
+    return true;
+  }
+  {
+    // SmoothPlastic (plastic.cpp): sampleComponent (:451-466) picks the Dirac reflection with probability pS (weight
+    // ks F / pS after the division by pdfComponent, discrete pdf pS: a specular vertex like a mirror's) or the diffuse base
+    // (sample.x rescaled; weight = kd' (1 - Fi)(1 - Fo) / eta^2 / (1 - pS), pdf = cos / pi (1 - pS))
+    const double eta = pm.coatEta, Fdr = pm.fdr, sw = pm.specWeight, cosWi = dot(n, wi);
+    const double Fi = dielectricFresnel(cosWi, eta);
+    const double pS = Fi * sw / (Fi * sw + (1 - Fi) * (1 - sw));
+    if (a < pS) {
+      wo = n * (2.0 * cosWi) - wi;
+      weight = pm.spec * (Fi / pS);
+      pdf = pS;
+      comp = 0x00008u;  // (as MAT_MIRROR's)
+      compSel = 0;
+      solidAngle = false;
+    } else {
+      wo = toWorld(n, cosineHemisphere((a - pS) / (1 - pS), b));
+      const double cosWo = dot(n, wo);
+      if (cosWo <= 0) return false;
+      const double Fo = dielectricFresnel(cosWo, eta), nl = pm.nonlinear;
+      const V3 kd = pm.albedo;
+      const V3 kdp(kd.x / (1 - (nl != 0 ? kd.x : 1.0) * Fdr), kd.y / (1 - (nl != 0 ? kd.y : 1.0) * Fdr), kd.z / (1 - (nl != 0 ? kd.z : 1.0) * Fdr));
+      weight = kdp * ((1 - Fi) * (1 - Fo) / (eta * eta) / (1 - pS));
+      pdf = cosWo * kInvPi * (1 - pS);
+      comp = GVPM_BSDF_DIFFUSE_REFLECTION;
+      compSel = 1;
+    }
+    if (maxc(weight) <= 0 || !(pdf > 0)) return false;
+    return true;
+  }
+}
+#endif
 
 // One light path; mirrors Path::randomWalk(scene, sampler, maxDepth, rrDepth, EImportance)
 // The walk in two pieces, so that a GPU lane whose path has ended can begin the next one while its neighbours walk on
@@ -441,6 +595,8 @@ template <class PATH> GVPM_HD inline bool walkStep(const SceneView &sc, Philox &
         cur.pdf = pdfM / (4.0 * std::fabs(woM));
         cur.comp = 0x00008u;  // EGlossyReflection
         if (maxc(cur.weight) <= 0 || !(cur.pdf > 0)) return false;
+      } else if (cur.matKind == MAT_ROUGHPLASTIC || cur.matKind == MAT_PLASTIC) {
+        if (!samplePlastic(sc.mats[cur.mat], cur.n, wi, a, b, wo, cur.weight, cur.pdf, cur.comp, cur.compSel, solidAngle)) return false;
 #endif
       } else {
         V3 local = cosineHemisphere(a, b);
@@ -556,7 +712,13 @@ GVPM_HD inline bool vertexIsDiffuse(const SceneView &sc, const LVertex &v) {
     case VT_EMITTER: return true;
     // (Phong: the Beckmann-equivalent roughness sqrt(2 / (2 + exponent)) of its glossy lobe, phong.cpp:293-300, is far
     // above bounceRoughness = 0.001 for every exponent the both-components branch admits)
-    case VT_SURFACE: return v.matKind == MAT_LAMBERT || v.matKind == MAT_PHONG || v.matKind == MAT_ROUGHCONDUCTOR || v.matKind == MAT_WARD;
+    // (rough plastic: alpha or infinity, both above bounceRoughness; smooth plastic: its diffuse component (roughness infinity),
+    // not its Dirac one (roughness 0) -- the roughness of the component the vertex was sampled through)
+    case VT_SURFACE:
+#if GVPM_SYNTH_GLOSSY
+      if (v.matKind == MAT_ROUGHPLASTIC || (v.matKind == MAT_PLASTIC && v.compSel == 1)) return true;
+#endif
+      return v.matKind == MAT_LAMBERT || v.matKind == MAT_PHONG || v.matKind == MAT_ROUGHCONDUCTOR || v.matKind == MAT_WARD;
     case VT_MEDIUM: return !(sc.medium.g > 0.5);
     default: return false;
   }
@@ -570,6 +732,16 @@ GVPM_HD inline int typeShift(const SceneView &sc, const LPath &p, size_t c) {
   if ((size_t)b + 1 == c) return 1;
   if (p[c - 1].type == VT_MEDIUM) return 2;
   return 3;
+}
+
+// the table entry a vertex on a plastic surface names as a parent (-1: none -- not plastic, or met through the Dirac component):
+// the head of the component it was sampled through
+GVPM_HD inline int plasticEntry(const SceneView &sc, const LVertex &par) {
+#if GVPM_SYNTH_GLOSSY
+  if (par.matKind == MAT_ROUGHPLASTIC) return sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 + GVPM_RTRANS_ENTRIES : 0);
+  if (par.matKind == MAT_PLASTIC && par.compSel == 1) return sc.mats[par.mat].bsdf;
+#endif
+  return -1;
 }
 
 struct PhotonRec {
@@ -607,6 +779,12 @@ template <class PATH> GVPM_HD inline void fillParent(const SceneView &sc, const 
       ptype = GVPM_PARENT_SURFACE_BSDF;
       r.parentG = (float)(sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 : 0));  // (the entry of the component the vertex was sampled through)
     }
+#if GVPM_SYNTH_GLOSSY
+    if (plasticEntry(sc, par) >= 0) {
+      ptype = GVPM_PARENT_SURFACE_BSDF;
+      r.parentG = (float)plasticEntry(sc, par);
+    }
+#endif
   } else if (par.type == VT_MEDIUM) {
     ptype = GVPM_PARENT_MEDIUM;
     r.parentScat = V3(sc.medium.sigma_s[0], sc.medium.sigma_s[1], sc.medium.sigma_s[2]);
@@ -687,6 +865,15 @@ template <class RL> GVPM_HD inline void flattenPath(const SceneView &sc, const L
         r.parentG = (float)(sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 : 0));  // (the entry of the component the vertex was sampled through)
         comp = par.comp;  // the sampled lobe's type: EGlossyReflection or EDiffuseReflection (vertex.cpp:178-179)
       }
+#if GVPM_SYNTH_GLOSSY
+      if (plasticEntry(sc, par) >= 0) {
+        ptype = GVPM_PARENT_SURFACE_BSDF;
+        r.parentG = (float)plasticEntry(sc, par);
+        comp = par.comp;
+      } else if (par.matKind == MAT_PLASTIC) {
+        comp = 0x00008u;  // met through its Dirac component: as a mirror
+      }
+#endif
     } else if (par.type == VT_MEDIUM) {
       ptype = GVPM_PARENT_MEDIUM;
       r.parentScat = V3(sc.medium.sigma_s[0], sc.medium.sigma_s[1], sc.medium.sigma_s[2]);
@@ -788,6 +975,15 @@ template <class RL, bool BEAMS> struct StreamPath {
             r.parentG = (float)(sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 : 0));  // (the entry of the component the vertex was sampled through)
             comp = par.comp;
           }
+#if GVPM_SYNTH_GLOSSY
+          if (plasticEntry(sc, par) >= 0) {
+            ptype = GVPM_PARENT_SURFACE_BSDF;
+            r.parentG = (float)plasticEntry(sc, par);
+            comp = par.comp;
+          } else if (par.matKind == MAT_PLASTIC) {
+            comp = 0x00008u;
+          }
+#endif
         } else if (par.type == VT_MEDIUM) {
           ptype = GVPM_PARENT_MEDIUM;
           r.parentScat = V3(sc.medium.sigma_s[0], sc.medium.sigma_s[1], sc.medium.sigma_s[2]);

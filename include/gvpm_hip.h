@@ -45,7 +45,8 @@ extern "C" {
 #endif
 
 #define GVPM_ABI_VERSION 3  /* 2: gvpm_bsdf grew to 64 bytes (rough conductor), round 4; 3: gvpm_devgen_scene carries the
-                              sensor's rotation (cam_to_world), round 5 */
+                              sensor's rotation (cam_to_world), round 5.  Table kinds and entry points are ADDITIONS and
+                              do not bump it (GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC: same 64-byte gvpm_bsdf) */
 
 /* ---- status codes --------------------------------------------------------*/
 typedef enum gvpm_status {
@@ -209,8 +210,37 @@ typedef struct gvpm_medium {
  *                 = |H|^2 / (pi alpha^2 H.z^4)                variant 2, "balanced" (the plugin's default)
  *       pdf  = w E / (4 pi alpha^2 (Hn . wi) cos^3(theta_Hn)) + (1 - w) cos(theta_o) / pi,  Hn = H / |H|                :230-266
  *     `exponent` carries alpha, `sample_visible` the variant, `specular_sampling_weight` w; pdfComponent = 1.
+ *   GVPM_BSDF_ROUGHPLASTIC  src/bsdfs/roughplastic.cpp:326-437,532-586 with an isotropic, untextured Beckmann or GGX distribution:
+ *     a dielectric coating (component 0, EGlossyReflection) over a diffuse base (component 1, EDiffuseReflection).  With
+ *     H = normalize(wi + wo), D, G as for the rough conductor, F = fresnelDielectricExt(wi . H, eta) (libcore/util.cpp:659-689),
+ *     T(c) = the external rough transmittance at the surface's eta and alpha (rtrans.h:183-236 after setEta / setAlpha: 100
+ *     values over c^(1/4) in [0, 1], evalCubicInterp1D of libcore/spline.cpp:23-60, clamped to [0, 1]) and
+ *     Fdr = 1 - the internal diffuse transmittance:
+ *       eval(wi, wo) = specular F D G / (4 cos(theta_i)) + kd' / pi cos(theta_o) T(cos_i) T(cos_o) / eta^2
+ *         kd' = kd / (1 - kd Fdr) per channel [nonlinear] or kd / (1 - Fdr); kd = the photon's parent_scat
+ *       pS = p w / (p w + (1 - p) (1 - w)),  p = 1 - T(cos_i),  w = specular_sampling_weight
+ *       pdf(wi, wo)  = pS pdf_m + (1 - pS) cos(theta_o) / pi,  pdf_m = the rough conductor's pdf (either form)
+ *     both zero unless cos(theta_i), cos(theta_o) > 0.  Below roughness 0.05 sampleNext picks ONE component (sampleComponent,
+ *     :532-564) and the reconnection evaluates that component: eval = its term alone, pdf * pdfComponent = its term of the
+ *     mixture above (pdfComponent = pS or 1 - pS, :566-586).  Fields: `specular`, `exponent` = alpha (>= 1e-4), `distribution`,
+ *     `sample_visible`, `specular_sampling_weight` as for the rough conductor; eta[0] = eta (>= 1), eta[1] = Fdr (in [0, 1)),
+ *     k[0] = the component met, as a float: 0 both, 1 the glossy one alone, 2 the diffuse one alone (sampledComponentIndex + 1);
+ *     k[1] = 1 for `nonlinear`, else 0; the rest zero.  THE SLICE follows the entry in the table: the 7 entries behind a
+ *     rough-plastic head are raw -- 100 floats T_0..T_99 contiguous (knot j at c^(1/4) = j / 99), then 12 zero words -- and
+ *     belong to it: gvpm_upload_bsdfs refuses a head without them and any slice value that is not a normal float or zero in
+ *     [0, 1]; photons name HEAD indices only (a raw entry read as a head shows 0 or a word >= 2^23 as its kind: such a photon's
+ *     shift fails like any unknown index).  pS = 0 / 0 (T(cos_i) = 0 with w = 0, or T(cos_i) = 1 with w = 1: NaN in the
+ *     reference) is a failed shift here.  A cosine that rounding left above 1 is looked up at 1.
+ *   GVPM_BSDF_PLASTIC  src/bsdfs/plastic.cpp:245-307,451-477, always met one component at a time.  Its Dirac component is a
+ *     specular vertex (nothing reconnects through it); this kind is its DIFFUSE component (k[0] must be 2):
+ *       eval = kd' / pi cos(theta_o) (1 - F(cos_i)) (1 - F(cos_o)) / eta^2,  F = fresnelDielectricExt(., eta), kd' as above
+ *       pdf * pdfComponent = cos(theta_o) / pi (1 - pS),  pS = F(cos_i) w / (F(cos_i) w + (1 - F(cos_i)) (1 - w))
+ *     Fields: eta[0], eta[1] = Fdr (the plugin's closed-form m_fdrInt), k[0] = 2, k[1] = nonlinear,
+ *     `specular_sampling_weight`; no slice.
  * A surface parent outside the closed set stays what it was: the host flags the photon's shift type 0 (failed shift).   */
-enum { GVPM_BSDF_PHONG = 1, GVPM_BSDF_ROUGHCONDUCTOR = 2, GVPM_BSDF_WARD = 3 };
+enum { GVPM_BSDF_PHONG = 1, GVPM_BSDF_ROUGHCONDUCTOR = 2, GVPM_BSDF_WARD = 3, GVPM_BSDF_ROUGHPLASTIC = 4, GVPM_BSDF_PLASTIC = 5 };
+#define GVPM_RTRANS_KNOTS 100          /* values of a rough-plastic slice                                          */
+#define GVPM_RTRANS_ENTRIES 7          /* raw table entries behind a rough-plastic head (448 bytes)                */
 enum { GVPM_WARD_WARD = 0, GVPM_WARD_DUER = 1, GVPM_WARD_BALANCED = 2 };
 enum { GVPM_MICROFACET_BECKMANN = 0, GVPM_MICROFACET_GGX = 1 };
 typedef struct gvpm_bsdf {    /* 64 bytes */
@@ -220,7 +250,8 @@ typedef struct gvpm_bsdf {    /* 64 bytes */
   float specular_sampling_weight; /* Phong, Ward: m_specularSamplingWeight, phong.cpp:93-97, ward.cpp:158-162 */
   int32_t distribution;       /* rough conductor: GVPM_MICROFACET_*; Phong: sampled component + 1 (0 = both) */
   int32_t sample_visible;     /* rough conductor: m_sampleVisible (the pdf's form); Ward: GVPM_WARD_* variant */
-  float eta[3], k[3];         /* rough conductor: m_eta, m_k (relative to the exterior, roughconductor.cpp:181-191) */
+  float eta[3], k[3];         /* rough conductor: m_eta, m_k (relative to the exterior, roughconductor.cpp:181-191);
+                                 plastics: eta[0] = eta, eta[1] = Fdr, k[0] = component met (0 / 1 / 2), k[1] = nonlinear */
   float reserved[2];
 } gvpm_bsdf;
 

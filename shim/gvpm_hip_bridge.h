@@ -31,6 +31,7 @@
 
 #include "../../../bsdfs/ior.h"         /* src/bsdfs/ior.h: lookupIOR, as roughconductor.cpp:22-23 includes them   */
 #include "../../../bsdfs/microfacet.h"  /* src/bsdfs/microfacet.h: MicrofacetDistribution(const Properties &)      */
+#include "../../../bsdfs/rtrans.h"      /* src/bsdfs/rtrans.h: RoughTransmittance, as roughplastic.cpp includes it      */
 
 #include "gvpm_hip.h"  /* include/gvpm_hip.h of the gvpm-hip repository */
 
@@ -459,10 +460,18 @@ private:
     push3(m_soa.prefix_w, prefix);
     /* BSDF::eval of the parent = diffuse reflectance * INV_PI * cos (src/bsdfs/diffuse.cpp:110-127);
      * medium parent: sigma_s * phase (shift_diffuse.cpp:54-70)                                                      */
+    /* ORDER MATTERS: glossyIndex() first.  For a plastic it records, in m_plasticFtr, the coating's diffuse transmittance that
+     * parent_scat is divided by below.  A plastic that plasticIndex() refuses (eta < 1, anisotropic, black) has no such
+     * record and keeps kd * Ftr: harmless, makeFlags() flags its shift type 0 and nothing reads its parent_scat.          */
+    const int glossy = glossyIndex(par);
     Spectrum scat(0.f);
     if (par->isSurfaceInteraction()) {
       const Intersection &its = par->getIntersection();
       scat = its.getBSDF()->getDiffuseReflectance(its);
+      /* the plastics report their base's reflectance times the coating's diffuse transmittance (roughplastic.cpp:309-315,
+       * plastic.cpp:217-221); the table's formulas take the base's own kd (include/gvpm_hip.h)                          */
+      auto coat = m_plasticFtr.find(its.getBSDF());
+      if (coat != m_plasticFtr.end() && coat->second > 0) scat /= coat->second;
     } else if (par->isMediumInteraction()) {
       scat = par->getMediumSamplingRecord().sigmaS;
     }
@@ -472,7 +481,6 @@ private:
     m_soa.parent_pdf.push_back((float) par->pdf[EImportance]);       /* shift_volume_photon.cpp:463-470, area measure */
     m_soa.edge_pdf.push_back((float) e->pdf[EImportance]);           /* parentEdge->pdf[EImportance]                */
     m_soa.parent_rr.push_back((float) par->rrWeight);                /* shift_diffuse.cpp:111-112                   */
-    const int glossy = glossyIndex(par);
     m_soa.parent_g.push_back(par->isMediumInteraction()
                                  ? (float) par->getMediumSamplingRecord().getPhaseFunction()->getMeanCosine()
                                  : (glossy >= 0 ? (float) glossy : 0.f));   /* hg.cpp:112-114; a glossy surface parent:
@@ -496,6 +504,7 @@ private:
     const BSDF *bsdf = its.getBSDF();
     const std::string cls = bsdf->getClass()->getName();
     if (bsdf->getType() & BSDF::ESpatiallyVarying) return -1;
+    if (cls == "RoughPlastic" || cls == "SmoothPlastic") return plasticIndex(par, its, bsdf, cls == "RoughPlastic");
     if (cls != "Phong" && cls != "RoughConductor" && cls != "Ward") return -1;
     /* Ward (src/bsdfs/ward.cpp, round 5): isotropic (no EAnisotropic component: alphaU == alphaV, ward.cpp:144-146) and sampled with
      * both components (roughness alpha >= 0.05, :370-376); alpha through getRoughness (:360-368), the sampling weight through
@@ -551,6 +560,77 @@ private:
     m_bsdfsDirty = true;
     return (int) idx;
   }
+  /* RoughPlastic (src/bsdfs/roughplastic.cpp; untextured -- the ESpatiallyVarying test above -- so alpha is constant and
+   * isotropic, Beckmann or GGX) and the DIFFUSE component of SmoothPlastic (src/bsdfs/plastic.cpp; its Dirac component is a
+   * specular vertex: -1).  An entry per (BSDF, sampled component): k[0] = sampledComponentIndex + 1.  eta = intIOR / extIOR as
+   * the constructors read them (roughplastic.cpp:203-213, plastic.cpp: the same two lookups); w = lum(ks) / (lum(kd) + lum(ks))
+   * (roughplastic.cpp:275-277) from the two reflectances; rough: the slice by building a RoughTransmittance as configure()
+   * does (:281-299: setEta, setAlpha) and reading it at the 100 knots cos = (j / 99)^4, Fdr = 1 - the interior table's
+   * evalDiffuse(alpha) (:371); smooth: m_fdrInt = fresnelDiffuseReflectance(1 / eta, false) (plastic.cpp:194).  A head is
+   * followed by the GVPM_RTRANS_ENTRIES raw entries of its slice (include/gvpm_hip.h).                                   */
+  int plasticIndex(const PathVertex *par, const Intersection &its, const BSDF *bsdf, bool rough) {
+    const int component = (int) par->sampledComponentIndex;
+    if (component < -1 || component > 1 || (!rough && component != 1)) return -1;
+    const std::pair<const BSDF *, int> key(bsdf, component);
+    auto found = m_bsdfIndex.find(key);
+    if (found != m_bsdfIndex.end()) return (int) found->second;
+    const Properties &props = bsdf->getProperties();
+    const Float eta = lookupIOR(props, "intIOR", "polypropylene") / lookupIOR(props, "extIOR", "air");
+    if (!(eta >= 1)) return -1;   /* (a coating rarer than its surroundings: outside the table's range)                   */
+    gvpm_bsdf b;
+    memset(&b, 0, sizeof(b));
+    b.kind = rough ? GVPM_BSDF_ROUGHPLASTIC : GVPM_BSDF_PLASTIC;
+    Float cr, cg, cb;
+    const Spectrum ks = bsdf->getSpecularReflectance(its);
+    ks.toLinearRGB(cr, cg, cb);
+    b.specular[0] = (float) cr; b.specular[1] = (float) cg; b.specular[2] = (float) cb;
+    b.eta[0] = (float) eta;
+    b.k[0] = (float) (component + 1);
+    b.k[1] = props.getBoolean("nonlinear", false) ? 1.f : 0.f;
+    std::array<float, 16 * GVPM_RTRANS_ENTRIES> raw;
+    raw.fill(0.f);
+    Float Ftr;
+    if (rough) {
+      MicrofacetDistribution distr(props);
+      if (!distr.isIsotropic() || (distr.getType() != MicrofacetDistribution::EBeckmann && distr.getType() != MicrofacetDistribution::EGGX))
+        return -1;
+      const Float alpha = distr.getAlphaU();
+      b.exponent = (float) alpha;
+      b.distribution = distr.getType() == MicrofacetDistribution::EGGX ? GVPM_MICROFACET_GGX : GVPM_MICROFACET_BECKMANN;
+      b.sample_visible = distr.getSampleVisible() ? 1 : 0;
+      ref<RoughTransmittance> ext = new RoughTransmittance(distr.getType());
+      ref<RoughTransmittance> inte = ext->clone();
+      ext->setEta(eta);
+      inte->setEta(1 / eta);
+      ext->setAlpha(alpha);
+      for (int j = 0; j < GVPM_RTRANS_KNOTS; ++j) {
+        const Float x = (Float) j / (Float) (GVPM_RTRANS_KNOTS - 1);
+        raw[j] = (float) ext->eval(x * x * x * x);
+        if (raw[j] != 0.f && raw[j] < 1.17549435e-38f) raw[j] = 0.f;   /* (gvpm_upload_bsdfs takes no subnormal word) */
+      }
+      Ftr = ext->evalDiffuse(alpha);
+      b.eta[1] = (float) (1 - inte->evalDiffuse(alpha));
+    } else {
+      Ftr = 1 - fresnelDiffuseReflectance(eta, false);
+      b.eta[1] = (float) fresnelDiffuseReflectance(1 / eta, false);
+    }
+    /* getDiffuseReflectance = kd * Ftr (roughplastic.cpp:309-315, plastic.cpp:217-221)                                   */
+    const Float lumS = ks.getLuminance(), lumD = Ftr > 0 ? bsdf->getDiffuseReflectance(its).getLuminance() / Ftr : 0;
+    if (!(lumS + lumD > 0)) return -1;
+    b.specular_sampling_weight = (float) (lumS / (lumD + lumS));
+    m_plasticFtr[bsdf] = Ftr;
+    const uint32_t idx = (uint32_t) m_bsdfs.size();
+    m_bsdfs.push_back(b);
+    if (rough) {
+      gvpm_bsdf cont[GVPM_RTRANS_ENTRIES];
+      memcpy(cont, raw.data(), sizeof(cont));
+      for (const gvpm_bsdf &c : cont) m_bsdfs.push_back(c);
+    }
+    m_bsdfIndex[key] = idx;
+    m_bsdfsDirty = true;
+    return (int) idx;
+  }
+  std::map<const BSDF *, Float> m_plasticFtr;   /* plastic BSDF -> the diffuse transmittance its getDiffuseReflectance carries */
   std::map<std::pair<const BSDF *, int>, uint32_t> m_bsdfIndex;   /* (BSDF, sampled component) -> table entry */
   std::vector<gvpm_bsdf> m_bsdfs;
   bool m_bsdfsDirty = false;
