@@ -163,6 +163,8 @@ assert BSDF_DTYPE.itemsize == 64
 GVPM_BSDF_PHONG, GVPM_BSDF_ROUGHCONDUCTOR, GVPM_BSDF_WARD = 1, 2, 3
 GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC = 4, 5
 GVPM_RTRANS_KNOTS, GVPM_RTRANS_ENTRIES = 100, 7
+GVPM_BSDF_WARD_ANISO, GVPM_BSDF_ROUGHCONDUCTOR_ANISO = 6, 8   # (7 is not a kind)
+GVPM_ANISO_ENTRIES = 1
 
 GVPM_WARD_WARD, GVPM_WARD_DUER, GVPM_WARD_BALANCED = 0, 1, 2
 GVPM_MICROFACET_BECKMANN, GVPM_MICROFACET_GGX = 0, 1
@@ -190,6 +192,44 @@ def plastic_entry(kind, specular, eta, fdr, weight, component, alpha=0.0, distri
     b["eta"][0, :2] = eta, fdr
     b["k"][0, :2] = component, 1.0 if nonlinear else 0.0
     return b
+
+
+def aniso_entry(kind, specular, alpha_u, alpha_v, tangent, weight=0.0, variant=0, distribution=0, sample_visible=0, eta=0.0, k=0.0):
+    """head + frame entry of one GVPM_BSDF_WARD_ANISO (weight, variant) / GVPM_BSDF_ROUGHCONDUCTOR_ANISO (distribution,
+    sample_visible, eta, k) surface (include/gvpm_hip.h): the head has its isotropic sibling's fields with exponent = alphaU, the
+    frame entry is {tangent (world space, taken as given: unit to 1e-3 or the upload refuses it), alphaV, 12 zero words}"""
+    t = np.zeros(1 + GVPM_ANISO_ENTRIES, BSDF_DTYPE)
+    b = t[:1]
+    b["kind"], b["specular"], b["exponent"], b["specular_sampling_weight"] = kind, specular, alpha_u, weight
+    if kind == GVPM_BSDF_WARD_ANISO:
+        b["sample_visible"] = variant
+    else:
+        b["distribution"], b["sample_visible"], b["eta"], b["k"] = distribution, sample_visible, eta, k
+    raw = t.view(np.float32).reshape(-1, 16)
+    raw[1, 0:3] = tangent
+    raw[1, 3] = alpha_v
+    return t
+
+
+def frame_of(table, head):
+    """(tangent[3], alphaV) of the frame entry behind anisotropic head `head` of a table"""
+    raw = np.ascontiguousarray(table[head + 1:head + 2]).view(np.float32)
+    return raw[0:3].copy(), float(raw[3])
+
+
+def bsdf_heads(table):
+    """which entries of a BSDF table are heads (what a photon's parent_g may name): not the raw entries behind a rough-plastic
+    head (its transmittance slice) nor the frame entry behind an anisotropic one.  A table cut short inside such a run keeps
+    the head it has."""
+    table = np.asarray(table)
+    head = np.zeros(table.size, bool)
+    i = 0
+    while i < table.size:
+        head[i] = True
+        kind = table["kind"][i]
+        i += 1 + (GVPM_RTRANS_ENTRIES if kind == GVPM_BSDF_ROUGHPLASTIC
+                  else GVPM_ANISO_ENTRIES if kind in (GVPM_BSDF_WARD_ANISO, GVPM_BSDF_ROUGHCONDUCTOR_ANISO) else 0)
+    return head
 
 
 # compact camera-beam sets (include/gvpm_hip.h, "compact camera-beam sets")

@@ -422,8 +422,39 @@ int gvpm_upload_bsdfs(gvpm_context *h, const gvpm_bsdf *table, uint32_t n) {
             return fail(h, GVPM_ERR_INVALID_ARG, "rough plastic: slice values are finite, in [0, 1] and not subnormal; 12 zero words behind them");
         }
       }
+    } else if (b.kind == GVPM_BSDF_WARD_ANISO || b.kind == GVPM_BSDF_ROUGHCONDUCTOR_ANISO) {
+      // a head with the fields of its isotropic sibling (exponent = alphaU) and ONE raw entry behind it: {s, alphaV, 0 x 12}
+      const bool ward = b.kind == GVPM_BSDF_WARD_ANISO;
+      if (n - i <= (uint32_t)GVPM_ANISO_ENTRIES)
+        return fail(h, GVPM_ERR_INVALID_ARG, "anisotropic Ward / rough conductor: the frame entry behind the head is missing");
+      float raw[16 * GVPM_ANISO_ENTRIES];
+      memcpy(raw, &table[i + 1], sizeof raw);
+      for (int j = 0; j < 16 * GVPM_ANISO_ENTRIES; ++j) {
+        // (+0 or a NORMAL float: a raw entry's first word must never read as a kind)
+        uint32_t bits;
+        memcpy(&bits, &raw[j], 4);
+        const bool okv = j < 4 ? (bits == 0u || (fabsf(raw[j]) >= FLT_MIN && fabsf(raw[j]) <= FLT_MAX)) : bits == 0u;
+        if (!okv)
+          return fail(h, GVPM_ERR_INVALID_ARG, "frame entry: tangent and alphaV are +0 or normal floats; 12 zero words behind them");
+      }
+      const double sl = std::sqrt((double)raw[0] * raw[0] + (double)raw[1] * raw[1] + (double)raw[2] * raw[2]);
+      if (!(std::fabs(sl - 1.0) <= 1e-3)) return fail(h, GVPM_ERR_INVALID_ARG, "frame entry: the tangent is a unit vector (to 1e-3)");
+      const float alphaV = raw[3];
+      // (alpha >= 1e-4: the microfacet constructor's clamp, microfacet.h:88-90; for Ward this library's own limit)
+      if (!(b.exponent >= 1e-4f) || !(alphaV >= 1e-4f))
+        return fail(h, GVPM_ERR_INVALID_ARG, "anisotropic Ward / rough conductor: alphaU, alphaV >= 1e-4");
+      if (ward) {
+        // (both components: Ward::getRoughness = 0.5 (alphaU + alphaV), ward.cpp:365, against sampleComponent, :370-389)
+        if (!(0.5f * (b.exponent + alphaV) >= 0.05f) || !(b.specular_sampling_weight >= 0.f && b.specular_sampling_weight <= 1.f))
+          return fail(h, GVPM_ERR_INVALID_ARG, "Ward: 0.5 (alphaU + alphaV) >= 0.05 (both components) and a sampling weight in [0, 1]");
+        if (b.sample_visible < GVPM_WARD_WARD || b.sample_visible > GVPM_WARD_BALANCED || b.distribution != 0)
+          return fail(h, GVPM_ERR_UNSUPPORTED, "Ward: variant ward / ward-duer / balanced, both components");
+      } else if (b.distribution != GVPM_MICROFACET_BECKMANN && b.distribution != GVPM_MICROFACET_GGX) {
+        return fail(h, GVPM_ERR_UNSUPPORTED, "rough conductor: Beckmann or GGX");
+      }
     } else {
-      return fail(h, GVPM_ERR_UNSUPPORTED, "bsdf kind outside the device's closed set (Phong, rough conductor, Ward, the plastics)");
+      return fail(h, GVPM_ERR_UNSUPPORTED,
+                  "bsdf kind outside the device's closed set (Phong, rough conductor, Ward, the plastics, anisotropic Ward / rough conductor)");
     }
     rows[4 * i] = make_float4(kindBits, b.specular[0], b.specular[1], b.specular[2]);
     rows[4 * i + 1] = make_float4(b.exponent, b.specular_sampling_weight, distBits, visBits);
@@ -432,6 +463,10 @@ int gvpm_upload_bsdfs(gvpm_context *h, const gvpm_bsdf *table, uint32_t n) {
     if (b.kind == GVPM_BSDF_ROUGHPLASTIC) {
       memcpy(&rows[4 * (size_t)i + 4], &table[i + 1], GVPM_RTRANS_ENTRIES * sizeof(gvpm_bsdf));
       i += GVPM_RTRANS_ENTRIES;
+    }
+    if (b.kind == GVPM_BSDF_WARD_ANISO || b.kind == GVPM_BSDF_ROUGHCONDUCTOR_ANISO) {
+      memcpy(&rows[4 * (size_t)i + 4], &table[i + 1], GVPM_ANISO_ENTRIES * sizeof(gvpm_bsdf));
+      i += GVPM_ANISO_ENTRIES;
     }
   }
   // once per scene: waits for whatever still reads the old table (as gvpm_upload_materials does)

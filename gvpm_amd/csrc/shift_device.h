@@ -454,6 +454,38 @@ __device__ __forceinline__ float microfacetG1(int ggx, float alpha, float cV, fl
   const float a2 = a * a;
   return fdiv(3.535f * a + 2.181f * a2, 1.f + 2.276f * a + 2.577f * a2);
 }
+// The anisotropic kinds (GVPM_BSDF_WARD_ANISO, GVPM_BSDF_ROUGHCONDUCTOR_ANISO): the frame entry behind the head carries the
+// surface's tangent s and alphaV; with the record's parent normal n, s' = normalize(s - n (n . s)) and t = n x s' stand for the
+// shading frame's s and t.  Only SQUARES of the tangential components enter the formulas, so neither the sign of s nor the
+// handedness of (s', t, n) matters.  False: the tangent is parallel to the normal -- a failed shift.
+__device__ __forceinline__ bool anisoFrame(const float4 fr, f3 n, f3 &s, f3 &t) {
+  s = mk3(fr.x, fr.y, fr.z);
+  s = s - n * dot(n, s);
+  const float ss = dot(s, s);
+  if (ss < 1e-12f) return false;
+  s = s * frsq(ss);
+  t = cross(n, s);
+  return true;
+}
+// MicrofacetDistribution::eval with alphaU != alphaV (microfacet.h:191-232): mx, my, cH = the unit half vector in the frame
+__device__ __forceinline__ float microfacetDAniso(int ggx, float au, float av, float mx, float my, float cH) {
+  if (cH <= 0.f) return 0.f;
+  const float c2 = cH * cH, ux = fdiv(mx, au), uy = fdiv(my, av);
+  const float e = fdiv(ux * ux + uy * uy, c2);
+  float r;
+  if (ggx) {
+    const float root = (1.f + e) * c2;
+    r = frcp(3.14159265358979323846f * au * av * root * root);
+  } else {
+    r = fdiv(__expf(-e), 3.14159265358979323846f * au * av * c2 * c2);
+  }
+  return r * cH < 1e-20f ? 0.f : r;
+}
+// projectRoughness (microfacet.h:541-551) of a unit direction with tangential components vx, vy and cosine cV; at
+// perpendicular incidence (sin^2 <= 0) the value is not used: microfacetG1 returns 1 before it reads alpha (:484-488)
+__device__ __forceinline__ float projectRoughness(float au, float av, float vx, float vy, float cV) {
+  return fsqrt(fdiv(vx * vx * (au * au) + vy * vy * (av * av), 1.f - cV * cV));
+}
 // fresnelConductorExact, one channel (src/libcore/util.cpp:747-769)
 __device__ __forceinline__ float fresnelConductor(float cI, float eta, float k) {
   const float c2 = cI * cI, s2 = 1.f - c2, s4 = s2 * s2;
@@ -531,14 +563,28 @@ __device__ __forceinline__ bool glossyParentEval(const GatherArgs &a, float inde
     }
     return true;
   }
-  if (kind == GVPM_BSDF_WARD) {
-    // src/bsdfs/ward.cpp:178-266, isotropic (alphaU == alphaV = b1.x), both components (roughness >= 0.05); H NOT normalised in
-    // eval, as the reference has it; the variant rides in the field the rough conductor uses for its pdf's form
-    const float al = b1.x, w = b1.y, ia2 = frcp(al * al);
+  if (kind == GVPM_BSDF_WARD || kind == GVPM_BSDF_WARD_ANISO) {
+    // src/bsdfs/ward.cpp:178-266, both components (roughness >= 0.05); H NOT normalised in eval, as the reference has it; the
+    // variant rides in the field the rough conductor uses for its pdf's form.  Isotropic: alphaU == alphaV = b1.x.
+    // Anisotropic: alphaU = b1.x, alphaV and the tangent in the frame entry behind the head; alphaU alphaV stands where
+    // alpha^2 stood, and the exponent -((H.x / alphaU)^2 + (H.y / alphaV)^2) / H.z^2 is scale-free in H: eval and pdf share it
+    const float w = b1.y;
     const int variant = __float_as_int(b1.w);
     const f3 H = wi + wo;
     const float HH = dot(H, H), Hz = cosWi + cosWo;
-    const float E = __expf(-(HH - Hz * Hz) * frcp(Hz * Hz) * ia2);
+    float ia2, ex;
+    if (kind == GVPM_BSDF_WARD) {
+      ia2 = frcp(b1.x * b1.x);
+      ex = -(HH - Hz * Hz) * frcp(Hz * Hz) * ia2;
+    } else {
+      const float4 fr = a.bsdfs[4 * (bi + 1)];
+      f3 s, t;
+      if (!anisoFrame(fr, n, s, t)) return false;
+      const float ux = fdiv(dot(H, s), b1.x), uy = fdiv(dot(H, t), fr.w);
+      ia2 = frcp(b1.x * fr.w);
+      ex = -(ux * ux + uy * uy) * frcp(Hz * Hz);
+    }
+    const float E = __expf(ex);
     const float INV_FOURPI = 0.07957747154594766788f;
     float factor1;
     if (variant == GVPM_WARD_WARD) factor1 = INV_FOURPI * ia2 * frsq(cosWi * cosWo);
@@ -551,16 +597,28 @@ __device__ __forceinline__ bool glossyParentEval(const GatherArgs &a, float inde
     pdf = w * (INV_FOURPI * ia2 * E * frcp(wiH * cH * cH * cH)) + (1.f - w) * (INV_PI_F * cosWo);
     return true;
   }
-  if (kind == GVPM_BSDF_ROUGHCONDUCTOR) {
+  if (kind == GVPM_BSDF_ROUGHCONDUCTOR || kind == GVPM_BSDF_ROUGHCONDUCTOR_ANISO) {
     const float4 b2 = a.bsdfs[4 * bi + 2], b3 = a.bsdfs[4 * bi + 3];
     const float alpha = b1.x;
     const int ggx = __float_as_int(b1.z) == GVPM_MICROFACET_GGX, vis = __float_as_int(b1.w) != 0;
     f3 H = wi + wo;
     H = H * frsq(dot(H, H));
     const float cH = dot(H, n), wiH = dot(wi, H), woH = dot(wo, H);
-    const float D = microfacetD(ggx, alpha, cH);
+    float D, alI = alpha, alO = alpha;  // (anisotropic: alphaU = b1.x, the roughness projected on wi and on wo)
+    if (kind == GVPM_BSDF_ROUGHCONDUCTOR) {
+      D = microfacetD(ggx, alpha, cH);
+    } else {
+      const float4 fr = a.bsdfs[4 * (bi + 1)];
+      f3 s, t;
+      if (!anisoFrame(fr, n, s, t)) return false;
+      D = microfacetDAniso(ggx, alpha, fr.w, dot(H, s), dot(H, t), cH);
+      if (D != 0.f) {
+        alI = projectRoughness(alpha, fr.w, dot(wi, s), dot(wi, t), cosWi);
+        alO = projectRoughness(alpha, fr.w, dot(wo, s), dot(wo, t), cosWo);
+      }
+    }
     if (D == 0.f) return true;  // eval and pdf both zero (pdfAll = D cos_H, pdfVisible = D G1 ...)
-    const float G1i = microfacetG1(ggx, alpha, cosWi, wiH), G1o = microfacetG1(ggx, alpha, cosWo, woH);
+    const float G1i = microfacetG1(ggx, alI, cosWi, wiH), G1o = microfacetG1(ggx, alO, cosWo, woH);
     const float model = fdiv(D * G1i * G1o, 4.f * cosWi);
     f = mk3(fresnelConductor(wiH, b2.x, b2.w) * b0.y, fresnelConductor(wiH, b2.y, b3.x) * b0.z,
             fresnelConductor(wiH, b2.z, b3.y) * b0.w) * model;

@@ -50,6 +50,8 @@ def lib():
         L.gvpm_synth_set_rtrans.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float]
         L.gvpm_synth_sample_plastic.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gvpm_synth_sample_aniso.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
         L.gvpm_synth_sensor.argtypes = [C.c_void_p, C.POINTER(abi.Sensor)]
         L.gvpm_synth_jitter.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
         _LIB = L
@@ -130,6 +132,18 @@ class SynthScene:
         if rc < 0:
             raise ValueError(f"sample_plastic({mat}): not a plastic material, or its slice is missing")
         return (wo, weight, pdf.value, comp.value) if rc == 1 else None
+
+    def sample_aniso(self, mat, n, wi, u1, u2):
+        """one bounce off anisotropic Ward / rough-conductor material `mat` as the light-path walk takes it (the material's own
+        tangent and alphas): (wo, weight, pdf) or None when the sample is lost"""
+        n, wi = np.ascontiguousarray(n, np.float64), np.ascontiguousarray(wi, np.float64)
+        wo, weight = np.zeros(3), np.zeros(3)
+        pdf = C.c_double(0)
+        rc = lib().gvpm_synth_sample_aniso(self._h, mat, n.ctypes.data, wi.ctypes.data, u1, u2, wo.ctypes.data, weight.ctypes.data,
+                                           C.addressof(pdf))
+        if rc < 0:
+            raise ValueError(f"sample_aniso({mat}): not an anisotropic material")
+        return (wo, weight, pdf.value) if rc == 1 else None
 
     def sensor(self):
         """the scene's pinhole sensor (gvpm_sensor) the compact beam sets are decoded with"""

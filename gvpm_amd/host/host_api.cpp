@@ -1,5 +1,7 @@
 #include "host_api.h"
 
+#include <cfloat>
+#include <cmath>
 #include <vector>
 
 #include "synth.h"
@@ -178,6 +180,20 @@ int gvpm_synth_sample_plastic(const gvpm_synth *s, int mat, const double *n, con
   return 1;
 }
 
+int gvpm_synth_sample_aniso(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
+                            double *weight, double *pdf) {
+  using namespace gvpm;
+  if (!s || !n || !wi || !wo || !weight || !pdf || mat < 0 || mat >= (int)s->scene.mats.size()) return GVPM_ERR_INVALID_ARG;
+  const SynthMat &pm = s->scene.mats[mat];
+  if (pm.kind != MAT_WARD_ANISO && pm.kind != MAT_ROUGHCONDUCTOR_ANISO) return GVPM_ERR_INVALID_ARG;
+  V3 o, w;
+  uint32_t comp = 0;
+  if (!sampleAniso(pm, V3(n[0], n[1], n[2]), V3(wi[0], wi[1], wi[2]), u1, u2, o, w, *pdf, comp)) return 0;
+  wo[0] = o.x; wo[1] = o.y; wo[2] = o.z;
+  weight[0] = w.x; weight[1] = w.y; weight[2] = w.z;
+  return 1;
+}
+
 uint32_t gvpm_synth_bsdfs(const gvpm_synth *s, gvpm_bsdf *out, uint32_t cap) {
   if (!s) return 0;
   uint32_t n = 0;
@@ -204,6 +220,34 @@ uint32_t gvpm_synth_bsdfs(const gvpm_synth *s, gvpm_bsdf *out, uint32_t cap) {
         }
         n += stride;
       }
+      continue;
+    }
+    if (m.kind == gvpm::MAT_WARD_ANISO || m.kind == gvpm::MAT_ROUGHCONDUCTOR_ANISO) {
+      // a head with the fields of its isotropic sibling (exponent = alphaU), then the frame entry {tangent, alphaV, 0 x 12}
+      const int stride = 1 + GVPM_ANISO_ENTRIES;
+      if (out && (uint32_t)(m.bsdf + stride) <= cap) {
+        gvpm_bsdf *b = &out[m.bsdf];
+        memset(b, 0, stride * sizeof(gvpm_bsdf));
+        b->specular[0] = (float)m.spec.x; b->specular[1] = (float)m.spec.y; b->specular[2] = (float)m.spec.z;
+        b->exponent = (float)m.exponent;
+        if (m.kind == gvpm::MAT_WARD_ANISO) {
+          b->kind = GVPM_BSDF_WARD_ANISO;
+          b->specular_sampling_weight = (float)m.specWeight;
+          b->sample_visible = m.distribution;  // (the model variant)
+        } else {
+          b->kind = GVPM_BSDF_ROUGHCONDUCTOR_ANISO;
+          b->distribution = m.distribution;
+          b->sample_visible = 0;  // (the host walk samples all normals, synth_core.h)
+          b->eta[0] = (float)m.eta.x; b->eta[1] = (float)m.eta.y; b->eta[2] = (float)m.eta.z;
+          b->k[0] = (float)m.k.x; b->k[1] = (float)m.k.y; b->k[2] = (float)m.k.z;
+        }
+        // (a frame word is +0 or a normal float, gvpm_upload_bsdfs: a component that rounds below FLT_MIN becomes +0)
+        float frame[4] = {(float)m.tangent.x, (float)m.tangent.y, (float)m.tangent.z, (float)m.alphaV};
+        for (float &v : frame)
+          if (!(std::fabs(v) >= FLT_MIN)) v = 0.f;
+        memcpy(b + 1, frame, sizeof frame);
+      }
+      n += stride;
       continue;
     }
     for (int c = 0; c < entries; ++c) {

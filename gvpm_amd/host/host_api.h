@@ -44,7 +44,14 @@ int gvpm_synth_set_rtrans(gvpm_synth *s, int mat, const float *values, int n, fl
  * 0 when the sample is lost, GVPM_ERR_INVALID_ARG for another kind of material or a missing slice. */
 int gvpm_synth_sample_plastic(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
                               double *weight, double *pdf, int *component);
-/* the BSDF table of the scene's glossy walls (a rough-plastic head is followed by the raw entries of its slice), in the order the photons' parent_g name them (gvpm_upload_bsdfs);
+/* A TEST HOOK like gvpm_synth_sample_plastic, for the anisotropic Ward / rough-conductor materials (scenes cbox_ward_aniso,
+ * cbox_conductor_aniso; synth_core.h sampleAniso): one bounce with the material's own tangent and alphas.  Returns 1 and wo,
+ * weight (eval / pdf), pdf (solid angle), 0 when the sample is lost (a tangent parallel to n among the reasons),
+ * GVPM_ERR_INVALID_ARG for another kind of material. */
+int gvpm_synth_sample_aniso(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
+                            double *weight, double *pdf);
+/* the BSDF table of the scene's glossy walls (a rough-plastic head is followed by the raw entries of its slice, an anisotropic head by its
+ * frame entry), in the order the photons' parent_g name them (gvpm_upload_bsdfs);
  * returns the number of entries (at most cap are written) */
 uint32_t gvpm_synth_bsdfs(const gvpm_synth *s, gvpm_bsdf *out, uint32_t cap);
 /* self-check of the streaming flattening the device generator uses (StreamPath, synth_core.h) against flattenPath /

@@ -244,6 +244,40 @@ bool makeScene(const std::string &fullName, int width, int height, uint32_t seed
     if (rot) addCornellBlocks(s, 0, mBack);
     setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);
     setMedium(s, 0.5, 0.5, 0.0);
+  } else if (name == "cbox_ward_aniso" || name == "cbox_conductor_aniso") {
+    // S-cbox with ANISOTROPIC walls (row f4): brushed surfaces, alphaU != alphaV, the brushing direction a per-material
+    // world-space tangent (the walls are planar; the `_rot` scenes turn it with everything else).  cbox_ward_aniso: the floor a
+    // balanced Ward lacquer (0.08 x 0.35), its tangent diagonal in the floor; the back wall the original Ward model (0.4 x 0.1),
+    // its tangent leaning out of the wall (the part along the normal is projected away, include/gvpm_hip.h).
+    // cbox_conductor_aniso: brushed copper floor (Beckmann 0.12 x 0.45), brushed aluminium back wall (GGX 0.35 x 0.08).
+    const bool ward = name == "cbox_ward_aniso";
+    auto aniso = [&](V3 kd, V3 ks, double alphaU, double alphaV, int distribution, V3 tangent, V3 eta, V3 k) {
+      auto lum = [](V3 c) { return 0.212671 * c.x + 0.715160 * c.y + 0.072169 * c.z; };  // Spectrum::getLuminance, RGB
+      SynthMat m{ward ? MAT_WARD_ANISO : MAT_ROUGHCONDUCTOR_ANISO, kd, ks, alphaU, ward ? lum(ks) / (lum(kd) + lum(ks)) : 0.0, 0};
+      m.alphaV = alphaV;
+      m.tangent = s.toWorld(normalize(tangent));
+      m.distribution = distribution;  // Ward: the variant; conductor: GVPM_MICROFACET_*
+      m.eta = eta;
+      m.k = k;
+      m.bsdf = 0;
+      for (const auto &q : s.mats) m.bsdf += bsdfSlots(q.kind, q.exponent);
+      s.mats.push_back(m);
+      return (int)s.mats.size() - 1;
+    };
+    int mFloor, mBack;
+    if (ward) {
+      mFloor = aniso(V3(0.3, 0.3, 0.3), V3(0.5, 0.5, 0.45), 0.08, 0.35, GVPM_WARD_BALANCED, V3(1.0, 0.0, 0.6), V3(0.0), V3(0.0));
+      mBack = aniso(V3(0.2, 0.25, 0.4), V3(0.3, 0.3, 0.3), 0.4, 0.1, GVPM_WARD_WARD, V3(0.9, 0.35, 0.25), V3(0.0), V3(0.0));
+    } else {
+      mFloor = aniso(V3(0.0), V3(1.0), 0.12, 0.45, GVPM_MICROFACET_BECKMANN, V3(1.0, 0.0, 0.6), V3(0.2004, 0.9240, 1.1022),
+                     V3(3.9129, 2.4528, 2.1421));
+      mBack = aniso(V3(0.0), V3(1.0), 0.35, 0.08, GVPM_MICROFACET_GGX, V3(0.9, 0.35, 0.25), V3(1.6574, 0.8803, 0.5212),
+                    V3(9.2238, 6.2695, 4.8370));
+    }
+    addBoxRoom(s, mFloor, 0, mBack, 1, 2, 3);
+    if (rot) addCornellBlocks(s, 0, 0);  // (white blocks: an anisotropic material sits on ONE plane, it has one tangent)
+    setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);
+    setMedium(s, 0.5, 0.5, 0.0);
   } else if (name == "cbox_roughplastic" || name == "cbox_roughplastic1" || name == "cbox_plastic") {
     // S-cbox with PLASTIC walls (row f4): floor and back wall a dielectric coating (eta 1.5) over a diffuse base --
     // src/bsdfs/roughplastic.cpp (floor Beckmann alpha 0.1, back wall GGX alpha 0.3; `1`: 0.03 / 0.04, below 0.05, so one

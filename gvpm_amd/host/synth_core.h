@@ -29,6 +29,9 @@ namespace gvpm {
 // derived from the reference's tables and does not live in this library).  Below roughness 0.05 one component per bounce.
 // MAT_PLASTIC: src/bsdfs/plastic.cpp, always one component per bounce: the Dirac reflection (a specular vertex, as a mirror's)
 // or the diffuse base (the table's GVPM_BSDF_PLASTIC entry); `fdr` = the closed-form m_fdrInt
+// MAT_WARD_ANISO, MAT_ROUGHCONDUCTOR_ANISO: the same two plugins with alphaU (`exponent`) != alphaV (`alphaV`) on a PLANAR
+// surface whose world-space tangent is `tangent` (the shading frame's s, the direction alphaU belongs to); the table's
+// GVPM_BSDF_WARD_ANISO / GVPM_BSDF_ROUGHCONDUCTOR_ANISO head + frame entry (include/gvpm_hip.h)
 // The glossy kinds are sampled by the HOST generators only: the device generator's closed set is Lambertian / index-matched /
 // mirror (gvpm_devgen_create refuses the others), and their fp64 pow / atan / log chains cost the device walk a third of its
 // time in registers alone when they were merely compiled in.
@@ -38,7 +41,7 @@ namespace gvpm {
 #define GVPM_SYNTH_GLOSSY 1
 #endif
 enum MatKind { MAT_LAMBERT = 0, MAT_NULL = 1, MAT_MIRROR = 2, MAT_PHONG = 3, MAT_ROUGHCONDUCTOR = 4, MAT_WARD = 5, MAT_ROUGHPLASTIC = 6,
-               MAT_PLASTIC = 7 };
+               MAT_PLASTIC = 7, MAT_WARD_ANISO = 8, MAT_ROUGHCONDUCTOR_ANISO = 9 };
 // table entries of a glossy material: PathVertex::sampleNext picks ONE component of a Phong surface below roughness 0.05
 // (vertex.cpp:160-165, Phong::getRoughness = sqrt(2 / (2 + exponent)), phong.cpp:293-300): an entry per component then
 GVPM_HD inline bool phongOneComponent(double exponent) { return sqrt(2.0 / (2.0 + exponent)) < 0.05; }
@@ -46,11 +49,13 @@ GVPM_HD inline bool phongOneComponent(double exponent) { return sqrt(2.0 / (2.0 
 // its diffuse component alone, the Dirac one is a specular vertex)
 GVPM_HD inline int bsdfEntries(int kind, double exponent) {
   if (kind == MAT_ROUGHPLASTIC) return exponent < 0.05 ? 2 : 1;
-  if (kind == MAT_PLASTIC) return 1;
+  if (kind == MAT_PLASTIC || kind == MAT_WARD_ANISO || kind == MAT_ROUGHCONDUCTOR_ANISO) return 1;
   return kind == MAT_PHONG ? (phongOneComponent(exponent) ? 2 : 1) : ((kind == MAT_ROUGHCONDUCTOR || kind == MAT_WARD) ? 1 : 0);
 }
-// table SLOTS of a material: a rough-plastic entry is a head followed by the raw entries of its slice (include/gvpm_hip.h)
+// table SLOTS of a material: a rough-plastic entry is a head followed by the raw entries of its slice, an anisotropic one a
+// head followed by its frame entry (include/gvpm_hip.h)
 GVPM_HD inline int bsdfSlots(int kind, double exponent) {
+  if (kind == MAT_WARD_ANISO || kind == MAT_ROUGHCONDUCTOR_ANISO) return 1 + GVPM_ANISO_ENTRIES;
   return bsdfEntries(kind, exponent) * (kind == MAT_ROUGHPLASTIC ? 1 + GVPM_RTRANS_ENTRIES : 1);
 }
 
@@ -74,6 +79,9 @@ struct SynthMat {
   int nonlinear = 0;
   // rough plastic: the transmittance slice, GVPM_RTRANS_KNOTS values in host memory owned by the SynthScene (null: not set yet)
   const float *rtrans = nullptr;
+  // the anisotropic kinds: alphaU = exponent, alphaV, and the surface's tangent in world space (a unit vector)
+  double alphaV = 0.0;
+  V3 tangent = V3(0.0);
 };
 
 // what the generators read of a scene (SynthScene::view(); the device gets the arrays in HBM)
@@ -135,6 +143,25 @@ GVPM_HD inline double conductorFresnel(double cI, double eta, double k) {
   const double Rs2 = (term1 - term2) / (term1 + term2);
   const double term3 = a2pb2 * c2 + s4, term4 = term2 * s2;
   return 0.5 * (Rs2 * (term3 - term4) / (term3 + term4) + Rs2);
+}
+// the same two terms with alphaU != alphaV (microfacet.h:191-232, :477-518 over projectRoughness, :541-551): (mx, my, cH) the
+// unit half vector in the shading frame, (vx, vy, cV) a unit direction in it
+GVPM_HD inline double conductorDAniso(int ggx, double au, double av, double mx, double my, double cH) {
+  if (cH <= 0) return 0;
+  const double c2 = cH * cH, e = (mx * mx / (au * au) + my * my / (av * av)) / c2;
+  double r;
+  if (ggx) {
+    const double root = (1 + e) * c2;
+    r = 1.0 / (kPi * au * av * root * root);
+  } else {
+    r = std::exp(-e) / (kPi * au * av * c2 * c2);
+  }
+  return r * cH < 1e-20 ? 0.0 : r;
+}
+GVPM_HD inline double projectedAlpha(double au, double av, double vx, double vy, double cV) {
+  const double s2 = 1 - cV * cV;
+  if (s2 <= 0) return au;
+  return std::sqrt((vx * vx * au * au + vy * vy * av * av) / s2);
 }
 // fresnelDielectricExt for a cosine >= 0 from outside a medium of relative index eta >= 1 (util.cpp:659-689)
 GVPM_HD inline double dielectricFresnel(double cI, double eta) {
@@ -275,6 +302,98 @@ GVPM_HD inline double hgEval(double g, double cosWiWo) {
 }
 
 #if GVPM_SYNTH_GLOSSY
+// One bounce off an anisotropic Ward / rough-conductor surface.  The shading frame is (s', t, n) with s' the material's tangent
+// projected into the surface and t = n x s' (what the device rebuilds from the table's frame entry).  (a, b) = (sample.x,
+// sample.y).  Ward::sample with bRec.component = -1 (ward.cpp:268-327; roughness 0.5 (alphaU + alphaV) >= 0.05): phiH / thetaH
+// as written at :289-306; RoughConductor::sample without visible normals over MicrofacetDistribution::sampleAll's anisotropic
+// branch (microfacet.h:287-347).  False: the sample is lost.
+inline bool sampleAniso(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
+  V3 sp = pm.tangent - n * dot(n, pm.tangent);
+  if (dot(sp, sp) < 1e-12) return false;
+  sp = normalize(sp);
+  const V3 tp = cross(n, sp);
+  const double au = pm.exponent, av = pm.alphaV, cosWi = dot(n, wi);
+  auto world = [&](double x, double y, double z) { return sp * x + tp * y + n * z; };
+  if (pm.kind == MAT_WARD_ANISO) {
+    const double sw = pm.specWeight;
+    double sx = a;
+    bool choseSpecular = true;
+    if (sx <= sw) {
+      sx /= sw;
+    } else {
+      sx = (sx - sw) / (1 - sw);
+      choseSpecular = false;
+    }
+    if (choseSpecular) {
+      double phiH = std::atan(av / au * std::tan(2.0 * kPi * b));
+      if (b > 0.5) phiH += kPi;
+      const double cosPhiH = std::cos(phiH), sinPhiH = std::sqrt(std::fmax(0.0, 1.0 - cosPhiH * cosPhiH));
+      const double thetaH =
+          std::atan(std::sqrt(std::fmax(0.0, -std::log(sx) / ((cosPhiH * cosPhiH) / (au * au) + (sinPhiH * sinPhiH) / (av * av)))));
+      const V3 H = world(std::sin(thetaH) * std::cos(phiH), std::sin(thetaH) * std::sin(phiH), std::cos(thetaH));
+      wo = H * (2.0 * dot(wi, H)) - wi;
+      comp = 0x00008u;  // EGlossyReflection
+    } else {
+      const V3 l = cosineHemisphere(sx, b);
+      wo = world(l.x, l.y, l.z);
+      comp = GVPM_BSDF_DIFFUSE_REFLECTION;
+    }
+    const double cosWo = dot(n, wo);
+    if (cosWo <= 0) return false;
+    // eval (H not normalised, as written) and pdf (normalised H): the exponent is scale-free in H
+    const V3 Hs = wi + wo;
+    const double HH = dot(Hs, Hs), Hz = cosWi + cosWo, f2 = dot(Hs, sp) / au, f3 = dot(Hs, tp) / av;
+    const double E = std::exp(-(f2 * f2 + f3 * f3) / (Hz * Hz));
+    double factor1;
+    if (pm.distribution == GVPM_WARD_WARD) factor1 = 1.0 / (4.0 * kPi * au * av * std::sqrt(cosWi * cosWo));
+    else if (pm.distribution == GVPM_WARD_DUER) factor1 = 1.0 / (4.0 * kPi * au * av * cosWi * cosWo);
+    else factor1 = HH / (kPi * au * av * Hz * Hz * Hz * Hz);
+    const double specRef = factor1 * E;
+    const double lenH = std::sqrt(HH), cH = Hz / lenH, wiH = dot(wi, Hs) / lenH;
+    const double specProb = E / (4.0 * kPi * au * av * wiH * cH * cH * cH);
+    const double pdfW = sw * specProb + (1 - sw) * cosWo * kInvPi;
+    if (pdfW == 0) return false;
+    const V3 f = (pm.spec * (specRef > 1e-10 ? specRef : 0.0) + pm.albedo * kInvPi) * cosWo;
+    weight = f * (1.0 / pdfW);
+    pdf = pdfW;
+    return maxc(weight) > 0;
+  }
+  // the rough conductor
+  const int ggx = pm.distribution == GVPM_MICROFACET_GGX;
+  const double phiM = std::atan(av / au * std::tan(kPi + 2 * kPi * b)) + kPi * std::floor(2 * b + 0.5);
+  const double sinPhiM = std::sin(phiM), cosPhiM = std::cos(phiM);
+  const double cosSc = cosPhiM / au, sinSc = sinPhiM / av, alphaSqr = 1.0 / (cosSc * cosSc + sinSc * sinSc);
+  double tanThetaMSqr, pdfM, cosThetaM;
+  if (ggx) {
+    tanThetaMSqr = alphaSqr * a / (1.0 - a);
+    cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
+    const double temp = 1 + tanThetaMSqr / alphaSqr;
+    pdfM = kInvPi / (au * av * cosThetaM * cosThetaM * cosThetaM * temp * temp);
+  } else {
+    tanThetaMSqr = alphaSqr * -std::log(1.0 - a);
+    cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
+    pdfM = (1.0 - a) / (kPi * au * av * cosThetaM * cosThetaM * cosThetaM);
+  }
+  if (!(pdfM >= 1e-20)) return false;
+  const double sinThetaM = std::sqrt(std::fmax(0.0, 1 - cosThetaM * cosThetaM));
+  const double mx = sinThetaM * cosPhiM, my = sinThetaM * sinPhiM;
+  const V3 m = world(mx, my, cosThetaM);
+  const double wiM = dot(wi, m);
+  wo = m * (2.0 * wiM) - wi;
+  const double cosWo = dot(n, wo);
+  if (cosWo <= 0) return false;
+  const double woM = dot(wo, m);
+  const double D = conductorDAniso(ggx, au, av, mx, my, cosThetaM);
+  const double G = conductorG1(ggx, projectedAlpha(au, av, dot(wi, sp), dot(wi, tp), cosWi), cosWi, wiM) *
+                   conductorG1(ggx, projectedAlpha(au, av, dot(wo, sp), dot(wo, tp), cosWo), cosWo, woM);
+  const double wgt = D * G * wiM / (pdfM * cosWi);
+  weight = V3(conductorFresnel(wiM, pm.eta.x, pm.k.x) * pm.spec.x, conductorFresnel(wiM, pm.eta.y, pm.k.y) * pm.spec.y,
+              conductorFresnel(wiM, pm.eta.z, pm.k.z) * pm.spec.z) * wgt;
+  pdf = pdfM / (4.0 * std::fabs(woM));
+  comp = 0x00008u;  // EGlossyReflection
+  return maxc(weight) > 0 && pdf > 0;
+}
+
 // One bounce off a plastic surface as PathVertex::sampleNext does it (vertex.cpp:160-173): component selection, BSDF::sample
 // with bRec.component, then weight /= pdfComponent, pdf *= pdfComponent.  (a, b): the vertex's two random numbers (sample.x,
 // sample.y).  False: the sample is lost (the walk ends).  solidAngle = false: a Dirac bounce, pdf in the discrete measure.
@@ -595,6 +714,8 @@ template <class PATH> GVPM_HD inline bool walkStep(const SceneView &sc, Philox &
         cur.pdf = pdfM / (4.0 * std::fabs(woM));
         cur.comp = 0x00008u;  // EGlossyReflection
         if (maxc(cur.weight) <= 0 || !(cur.pdf > 0)) return false;
+      } else if (cur.matKind == MAT_WARD_ANISO || cur.matKind == MAT_ROUGHCONDUCTOR_ANISO) {
+        if (!sampleAniso(sc.mats[cur.mat], cur.n, wi, a, b, wo, cur.weight, cur.pdf, cur.comp)) return false;
       } else if (cur.matKind == MAT_ROUGHPLASTIC || cur.matKind == MAT_PLASTIC) {
         if (!samplePlastic(sc.mats[cur.mat], cur.n, wi, a, b, wo, cur.weight, cur.pdf, cur.comp, cur.compSel, solidAngle)) return false;
 #endif
@@ -717,6 +838,7 @@ GVPM_HD inline bool vertexIsDiffuse(const SceneView &sc, const LVertex &v) {
     case VT_SURFACE:
 #if GVPM_SYNTH_GLOSSY
       if (v.matKind == MAT_ROUGHPLASTIC || (v.matKind == MAT_PLASTIC && v.compSel == 1)) return true;
+      if (v.matKind == MAT_WARD_ANISO || v.matKind == MAT_ROUGHCONDUCTOR_ANISO) return true;  // (alphas far above bounceRoughness)
 #endif
       return v.matKind == MAT_LAMBERT || v.matKind == MAT_PHONG || v.matKind == MAT_ROUGHCONDUCTOR || v.matKind == MAT_WARD;
     case VT_MEDIUM: return !(sc.medium.g > 0.5);
@@ -775,7 +897,8 @@ template <class PATH> GVPM_HD inline void fillParent(const SceneView &sc, const 
     ptype = GVPM_PARENT_SURFACE;
     r.parentScat = par.albedo;
     r.parentWi = normalize(path[ip - 1].pos - par.pos);
-    if (par.matKind == MAT_PHONG || par.matKind == MAT_ROUGHCONDUCTOR || par.matKind == MAT_WARD) {
+    if (par.matKind == MAT_PHONG || par.matKind == MAT_ROUGHCONDUCTOR || par.matKind == MAT_WARD || par.matKind == MAT_WARD_ANISO ||
+        par.matKind == MAT_ROUGHCONDUCTOR_ANISO) {  // (the anisotropic kinds: bsdf names the HEAD, the frame entry follows it)
       ptype = GVPM_PARENT_SURFACE_BSDF;
       r.parentG = (float)(sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 : 0));  // (the entry of the component the vertex was sampled through)
     }
@@ -860,7 +983,8 @@ template <class RL> GVPM_HD inline void flattenPath(const SceneView &sc, const L
       ptype = GVPM_PARENT_SURFACE;
       r.parentScat = par.albedo;
       r.parentWi = normalize(path[i - 2].pos - par.pos);
-      if (par.matKind == MAT_PHONG || par.matKind == MAT_ROUGHCONDUCTOR || par.matKind == MAT_WARD) {
+      if (par.matKind == MAT_PHONG || par.matKind == MAT_ROUGHCONDUCTOR || par.matKind == MAT_WARD || par.matKind == MAT_WARD_ANISO ||
+        par.matKind == MAT_ROUGHCONDUCTOR_ANISO) {  // (the anisotropic kinds: bsdf names the HEAD, the frame entry follows it)
         ptype = GVPM_PARENT_SURFACE_BSDF;
         r.parentG = (float)(sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 : 0));  // (the entry of the component the vertex was sampled through)
         comp = par.comp;  // the sampled lobe's type: EGlossyReflection or EDiffuseReflection (vertex.cpp:178-179)
@@ -970,7 +1094,8 @@ template <class RL, bool BEAMS> struct StreamPath {
           ptype = GVPM_PARENT_SURFACE;
           r.parentScat = par.albedo;
           r.parentWi = normalize(path[i - 2].pos - par.pos);
-          if (par.matKind == MAT_PHONG || par.matKind == MAT_ROUGHCONDUCTOR || par.matKind == MAT_WARD) {
+          if (par.matKind == MAT_PHONG || par.matKind == MAT_ROUGHCONDUCTOR || par.matKind == MAT_WARD || par.matKind == MAT_WARD_ANISO ||
+        par.matKind == MAT_ROUGHCONDUCTOR_ANISO) {  // (the anisotropic kinds: bsdf names the HEAD, the frame entry follows it)
             ptype = GVPM_PARENT_SURFACE_BSDF;
             r.parentG = (float)(sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 : 0));  // (the entry of the component the vertex was sampled through)
             comp = par.comp;

@@ -46,7 +46,7 @@ extern "C" {
 
 #define GVPM_ABI_VERSION 3  /* 2: gvpm_bsdf grew to 64 bytes (rough conductor), round 4; 3: gvpm_devgen_scene carries the
                               sensor's rotation (cam_to_world), round 5.  Table kinds and entry points are ADDITIONS and
-                              do not bump it (GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC: same 64-byte gvpm_bsdf) */
+                              do not bump it (GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC, the two _ANISO kinds: same 64-byte gvpm_bsdf) */
 
 /* ---- status codes --------------------------------------------------------*/
 typedef enum gvpm_status {
@@ -237,8 +237,35 @@ typedef struct gvpm_medium {
  *       pdf * pdfComponent = cos(theta_o) / pi (1 - pS),  pS = F(cos_i) w / (F(cos_i) w + (1 - F(cos_i)) (1 - w))
  *     Fields: eta[0], eta[1] = Fdr (the plugin's closed-form m_fdrInt), k[0] = 2, k[1] = nonlinear,
  *     `specular_sampling_weight`; no slice.
+ *   GVPM_BSDF_WARD_ANISO, GVPM_BSDF_ROUGHCONDUCTOR_ANISO  the anisotropic forms of GVPM_BSDF_WARD and GVPM_BSDF_ROUGHCONDUCTOR
+ *     (alphaU != alphaV allowed) on a PLANAR surface.  The photon record carries the parent's normal n and no tangent: the
+ *     tangent travels per surface in the table.  A head of either kind has the fields of its isotropic sibling, `exponent` =
+ *     alphaU, and is followed by ONE raw entry, the frame entry: words 0..2 = s, the world-space tangent of the surface (the
+ *     `s` of the intersection's shading frame, the direction alphaU belongs to), word 3 = alphaV, words 4..15 zero.  The
+ *     device forms  s' = normalize(s - n (n . s)),  t = n x s'  and, for a vector v,  v.x = v . s', v.y = v . t, v.z = v . n;
+ *     only SQUARES of the tangential components enter the formulas below, so neither the sign of s nor the handedness of
+ *     (s', t, n) matters.  |s - n (n . s)|^2 < 1e-12 (a tangent parallel to the normal) is a failed shift.
+ *       Ward (ward.cpp:178-264): with H = wi + wo (not normalised),  E = exp(-((H.x / alphaU)^2 + (H.y / alphaV)^2) / H.z^2)
+ *       (scale-free in H: eval and pdf use the same value), eval and pdf are those of GVPM_BSDF_WARD with alphaU alphaV in
+ *       the place of alpha^2 in factor1 and in the pdf; the `factor1 * E > 1e-10` rule is kept.
+ *       Rough conductor (roughconductor.cpp:257-319): with m = normalize(wi + wo),
+ *         D = exp(-e) / (pi alphaU alphaV cos^4(theta_m))  [Beckmann]   or   1 / (pi alphaU alphaV ((1 + e) cos^2(theta_m))^2)  [GGX],
+ *         e = (m.x^2 / alphaU^2 + m.y^2 / alphaV^2) / cos^2(theta_m);  D cos(theta_m) < 1e-20 -> D = 0           (microfacet.h:191-232)
+ *         smithG1(v, m) with alpha = projectRoughness(v) = sqrt((v.x^2 alphaU^2 + v.y^2 alphaV^2) / sin^2(theta_v))    (:477-522, :541-551)
+ *         (perpendicular incidence returns 1 before the projection), Fresnel and both forms of the pdf as for the isotropic kind.
+ *     gvpm_upload_bsdfs refuses, before anything is copied (GVPM_ERR_INVALID_ARG): a head without its frame entry; a frame
+ *     word that is not +0 or a normal float (-0, subnormals, NaN, inf: a raw entry read as a head then shows 0 or a word
+ *     >= 2^23 as its kind, never a valid one); | |s| - 1 | > 1e-3; alphaU or alphaV < 1e-4 (the microfacet constructor's clamp,
+ *     microfacet.h:88-90; for Ward, whose plugin has no clamp, it is THIS LIBRARY's own limit); Ward: 0.5 (alphaU + alphaV) <
+ *     0.05 (Ward::getRoughness, ward.cpp:365, against sampleComponent, :370-389: below it one component is sampled), a
+ *     sampling weight outside [0, 1]; GVPM_ERR_UNSUPPORTED: a Ward variant outside 0..2 or `distribution` != 0, a conductor
+ *     whose distribution is not Beckmann or GGX (the Phong / Ashikhmin-Shirley one).  alphaU == alphaV is legal: the isotropic
+ *     kind, whatever the tangent.  Photons name HEAD indices only.  GVPM_ANISO_ENTRIES = the raw entries behind such a head.
+ *     (7 is not a kind.)
  * A surface parent outside the closed set stays what it was: the host flags the photon's shift type 0 (failed shift).   */
-enum { GVPM_BSDF_PHONG = 1, GVPM_BSDF_ROUGHCONDUCTOR = 2, GVPM_BSDF_WARD = 3, GVPM_BSDF_ROUGHPLASTIC = 4, GVPM_BSDF_PLASTIC = 5 };
+enum { GVPM_BSDF_PHONG = 1, GVPM_BSDF_ROUGHCONDUCTOR = 2, GVPM_BSDF_WARD = 3, GVPM_BSDF_ROUGHPLASTIC = 4, GVPM_BSDF_PLASTIC = 5,
+       GVPM_BSDF_WARD_ANISO = 6, GVPM_BSDF_ROUGHCONDUCTOR_ANISO = 8 };
+#define GVPM_ANISO_ENTRIES 1           /* raw table entries behind an anisotropic head (the frame entry)            */
 #define GVPM_RTRANS_KNOTS 100          /* values of a rough-plastic slice                                          */
 #define GVPM_RTRANS_ENTRIES 7          /* raw table entries behind a rough-plastic head (448 bytes)                */
 enum { GVPM_WARD_WARD = 0, GVPM_WARD_DUER = 1, GVPM_WARD_BALANCED = 2 };
@@ -246,7 +273,7 @@ enum { GVPM_MICROFACET_BECKMANN = 0, GVPM_MICROFACET_GGX = 1 };
 typedef struct gvpm_bsdf {    /* 64 bytes */
   int32_t kind;               /* GVPM_BSDF_*                                                            */
   float specular[3];          /* m_specularReflectance (Phong: after ensureEnergyConservation, phong.cpp:86-91) */
-  float exponent;             /* Phong: m_exponent; rough conductor, Ward: alpha                        */
+  float exponent;             /* Phong: m_exponent; rough conductor, Ward: alpha (the _ANISO kinds: alphaU) */
   float specular_sampling_weight; /* Phong, Ward: m_specularSamplingWeight, phong.cpp:93-97, ward.cpp:158-162 */
   int32_t distribution;       /* rough conductor: GVPM_MICROFACET_*; Phong: sampled component + 1 (0 = both) */
   int32_t sample_visible;     /* rough conductor: m_sampleVisible (the pdf's form); Ward: GVPM_WARD_* variant */

@@ -24,6 +24,7 @@
 
 #include <array>
 #include <cctype>
+#include <cmath>
 #include <map>
 #include <vector>
 
@@ -506,12 +507,25 @@ private:
     if (bsdf->getType() & BSDF::ESpatiallyVarying) return -1;
     if (cls == "RoughPlastic" || cls == "SmoothPlastic") return plasticIndex(par, its, bsdf, cls == "RoughPlastic");
     if (cls != "Phong" && cls != "RoughConductor" && cls != "Ward") return -1;
-    /* Ward (src/bsdfs/ward.cpp, round 5): isotropic (no EAnisotropic component: alphaU == alphaV, ward.cpp:144-146) and sampled with
+    /* Ward (src/bsdfs/ward.cpp, round 5): isotropic (no EAnisotropic component: alphaU == alphaV, ward.cpp:144-146; the
+     * anisotropic plugin goes to anisoIndex() below) and sampled with
      * both components (roughness alpha >= 0.05, :370-376); alpha through getRoughness (:360-368), the sampling weight through
      * pdfComponent(component 0) (:391-402), the model variant from the plugin's own property (default "balanced", :103-113) */
-    if (cls == "Ward" && ((bsdf->getType() & BSDF::EAnisotropic) || par->sampledComponentIndex != -1)) return -1;
+    if (cls == "Ward" && par->sampledComponentIndex != -1) return -1;
     const int component = cls == "Phong" ? (int) par->sampledComponentIndex : -1;
     if (component < -1 || component > 1) return -1;
+    /* ANISOTROPIC Ward / rough conductor (alphaU != alphaV; untextured -- the ESpatiallyVarying test above -- so both alphas are
+     * constant): GVPM_BSDF_WARD_ANISO / GVPM_BSDF_ROUGHCONDUCTOR_ANISO, a head + its frame entry {s, alphaV}.  The photon record
+     * has no tangent: it travels per SURFACE, so the entry is keyed by (BSDF, sampled component, the vertex's shFrame.s
+     * quantised to 1e-3 per component).  A planar surface with planar UVs has one s; a surface that would need more than
+     * GVPM_SHIM_MAX_TANGENTS distinct ones (curved, or textured UVs) keeps shift type 0 from then on.                       */
+    const bool wardAniso = cls == "Ward" && (bsdf->getType() & BSDF::EAnisotropic);
+    bool condAniso = false;
+    if (cls == "RoughConductor") {
+      MicrofacetDistribution probe(bsdf->getProperties());
+      condAniso = !probe.isIsotropic();
+    }
+    if (wardAniso || condAniso) return anisoIndex(par, its, bsdf, wardAniso);
     const std::pair<const BSDF *, int> key(bsdf, component);
     auto found = m_bsdfIndex.find(key);
     if (found != m_bsdfIndex.end()) return (int) found->second;
@@ -560,6 +574,74 @@ private:
     m_bsdfsDirty = true;
     return (int) idx;
   }
+  /* Anisotropic Ward (both components: 0.5 (alphaU + alphaV) >= 0.05, ward.cpp:365,370-389 -- glossyIndex() has checked
+   * sampledComponentIndex == -1; alphaU / alphaV from the plugin's properties as its constructor reads them, :115-129) and
+   * anisotropic Beckmann / GGX rough conductors whose Properties name `eta` and `k`.  The head has the isotropic kind's
+   * fields with exponent = alphaU; the frame entry behind it holds the vertex's shFrame.s (world space) and alphaV.        */
+  enum { GVPM_SHIM_MAX_TANGENTS = 4 };
+  int anisoIndex(const PathVertex *par, const Intersection &its, const BSDF *bsdf, bool ward) {
+    const Vector s = its.shFrame.s;
+    const std::array<int, 3> q = {(int) std::lround(s.x * 1000), (int) std::lround(s.y * 1000), (int) std::lround(s.z * 1000)};
+    const std::pair<const BSDF *, std::array<int, 3>> key(bsdf, q);
+    auto found = m_anisoIndex.find(key);
+    if (found != m_anisoIndex.end()) return (int) found->second;
+    int &tangents = m_anisoTangents[bsdf];
+    if (tangents < 0 || tangents >= GVPM_SHIM_MAX_TANGENTS) {
+      tangents = -1;   /* curved, or textured UVs: outside the closed set */
+      return -1;
+    }
+    const Properties &props = bsdf->getProperties();
+    gvpm_bsdf b, frame;
+    memset(&b, 0, sizeof(b));
+    memset(&frame, 0, sizeof(frame));
+    Float cr, cg, cb;
+    bsdf->getSpecularReflectance(its).toLinearRGB(cr, cg, cb);
+    b.specular[0] = (float) cr; b.specular[1] = (float) cg; b.specular[2] = (float) cb;
+    Float alphaU, alphaV;
+    if (ward) {
+      if (!props.hasProperty("alphaU") || !props.hasProperty("alphaV")) return -1;   /* (textures come as children) */
+      alphaU = props.getFloat("alphaU");
+      alphaV = props.getFloat("alphaV");
+      if (!(alphaU >= 1e-4f && alphaV >= 1e-4f) || !(0.5f * (alphaU + alphaV) >= 0.05f)) return -1;
+      b.kind = GVPM_BSDF_WARD_ANISO;
+      BSDFSamplingRecord bRec(its, its.wi, its.wi, EImportance);
+      bRec.component = 0;
+      b.specular_sampling_weight = (float) bsdf->pdfComponent(bRec);
+      std::string variant = props.getString("variant", "balanced");
+      for (char &ch : variant) ch = (char) std::tolower((unsigned char) ch);
+      b.sample_visible = variant == "ward" ? GVPM_WARD_WARD : variant == "ward-duer" ? GVPM_WARD_DUER : GVPM_WARD_BALANCED;
+    } else {
+      if (!props.hasProperty("eta") || !props.hasProperty("k")) return -1;
+      MicrofacetDistribution distr(props);
+      if (distr.getType() != MicrofacetDistribution::EBeckmann && distr.getType() != MicrofacetDistribution::EGGX) return -1;
+      alphaU = distr.getAlphaU();   /* (after the constructor's clamp to >= 1e-4, microfacet.h:88-90) */
+      alphaV = distr.getAlphaV();
+      b.kind = GVPM_BSDF_ROUGHCONDUCTOR_ANISO;
+      b.distribution = distr.getType() == MicrofacetDistribution::EGGX ? GVPM_MICROFACET_GGX : GVPM_MICROFACET_BECKMANN;
+      b.sample_visible = distr.getSampleVisible() ? 1 : 0;
+      const Float extEta = lookupIOR(props, "extEta", "air");
+      const Spectrum eta = props.getSpectrum("eta") / extEta, k = props.getSpectrum("k") / extEta;
+      eta.toLinearRGB(cr, cg, cb);
+      b.eta[0] = (float) cr; b.eta[1] = (float) cg; b.eta[2] = (float) cb;
+      k.toLinearRGB(cr, cg, cb);
+      b.k[0] = (float) cr; b.k[1] = (float) cg; b.k[2] = (float) cb;
+    }
+    b.exponent = (float) alphaU;
+    /* frame words are +0 or normal floats (gvpm_upload_bsdfs takes no -0 and no subnormal word)                           */
+    float words[4] = {(float) s.x, (float) s.y, (float) s.z, (float) alphaV};
+    for (float &w : words)
+      if (!(std::fabs(w) >= 1.17549435e-38f)) w = 0.f;
+    memcpy(&frame, words, sizeof(words));
+    ++tangents;
+    const uint32_t idx = (uint32_t) m_bsdfs.size();
+    m_bsdfs.push_back(b);
+    m_bsdfs.push_back(frame);
+    m_anisoIndex[key] = idx;
+    m_bsdfsDirty = true;
+    return (int) idx;
+  }
+  std::map<std::pair<const BSDF *, std::array<int, 3>>, uint32_t> m_anisoIndex;   /* (BSDF, quantised shFrame.s) -> head */
+  std::map<const BSDF *, int> m_anisoTangents;   /* distinct tangents seen per BSDF; -1: too many, refused for good */
   /* RoughPlastic (src/bsdfs/roughplastic.cpp; untextured -- the ESpatiallyVarying test above -- so alpha is constant and
    * isotropic, Beckmann or GGX) and the DIFFUSE component of SmoothPlastic (src/bsdfs/plastic.cpp; its Dirac component is a
    * specular vertex: -1).  An entry per (BSDF, sampled component): k[0] = sampledComponentIndex + 1.  eta = intIOR / extIOR as
