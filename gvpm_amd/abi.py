@@ -46,7 +46,6 @@ GVPM_BSDF_DIFFUSE_REFLECTION = 0x00002
 GVPM_BSDF_ALL = 0x1FFFF
 
 GVPM_PARENT_EMITTER, GVPM_PARENT_SURFACE, GVPM_PARENT_MEDIUM, GVPM_PARENT_SURFACE_BSDF = 0, 1, 2, 3
-GVPM_BSDF_PHONG = 1
 GVPM_ACCUM_FLOATS = 27
 
 
@@ -166,6 +165,15 @@ GVPM_RTRANS_KNOTS, GVPM_RTRANS_ENTRIES = 100, 7
 GVPM_BSDF_WARD_ANISO, GVPM_BSDF_ROUGHCONDUCTOR_ANISO = 6, 8   # (7 is not a kind)
 GVPM_ANISO_ENTRIES = 1
 
+
+def bsdf_tail_entries(kind):
+    """raw table entries behind a head of `kind` (csrc/bsdf_table.h, bsdfTailEntries): a rough-plastic head's transmittance
+    slice, an anisotropic head's frame entry"""
+    if kind == GVPM_BSDF_ROUGHPLASTIC:
+        return GVPM_RTRANS_ENTRIES
+    return GVPM_ANISO_ENTRIES if kind in (GVPM_BSDF_WARD_ANISO, GVPM_BSDF_ROUGHCONDUCTOR_ANISO) else 0
+
+
 GVPM_WARD_WARD, GVPM_WARD_DUER, GVPM_WARD_BALANCED = 0, 1, 2
 GVPM_MICROFACET_BECKMANN, GVPM_MICROFACET_GGX = 0, 1
 
@@ -226,9 +234,7 @@ def bsdf_heads(table):
     i = 0
     while i < table.size:
         head[i] = True
-        kind = table["kind"][i]
-        i += 1 + (GVPM_RTRANS_ENTRIES if kind == GVPM_BSDF_ROUGHPLASTIC
-                  else GVPM_ANISO_ENTRIES if kind in (GVPM_BSDF_WARD_ANISO, GVPM_BSDF_ROUGHCONDUCTOR_ANISO) else 0)
+        i += 1 + bsdf_tail_entries(table["kind"][i])
     return head
 
 

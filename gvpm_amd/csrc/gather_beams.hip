@@ -354,7 +354,7 @@ __device__ __forceinline__ double shiftBeamDiffuse(const GatherArgs &a, const Ti
   const double newPBDist = sqrt(len2(newPBDir));
   newPBDir = newPBDir / newPBDist;
   // visibility over the whole new beam [Epsilon, newPBDist], shift_volume_beams.cpp:420-426
-  // (EXV: the exact pass -- every triangle test of the segment in fp64, shift_device.h anyHitExact)
+  // (EXV: the exact pass -- every triangle test of the segment in fp64, occlusion.h anyHitExact)
   if (EXV ? anyHitExact(a, tof(b.p1), newPBDir, (double)a.cfg.epsilon, newPBDist)
           : (anyHitScene<true>(a.bvh, a.tri4, a.ntri, tof(b.p1), tof(newPBDir), a.cfg.epsilon, (float)newPBDist) & 1) != 0)
     return 1.0;
@@ -370,7 +370,7 @@ __device__ __forceinline__ double shiftBeamDiffuse(const GatherArgs &a, const Ti
     thr = b.parentScat * (INV_PI * cosWo);
     pdfValueSA = INV_PI * cosWo;
     if (ptype == GVPM_PARENT_SURFACE_BSDF) {
-      // a glossy parent (gvpm_upload_bsdfs): Phong in fp64 (src/bsdfs/phong.cpp:121-186,331-342; shift_device.h phongEvalD)
+      // a glossy parent (gvpm_upload_bsdfs): Phong in fp64 (src/bsdfs/phong.cpp:121-186,331-342; parent_bsdf.h phongEvalD)
       if (!phongEvalD(a, (float)b.parentG, b.parentScat, b.parentN, b.parentWi, newPBDir, cosWi, cosWo, thr, pdfValueSA)) {
         // (the other table entries -- the rough conductor -- through the fp32 statement the default path uses)
         f3 ff;
@@ -741,7 +741,7 @@ constexpr uint32_t SCENE_LDS_TRIS = 128;
 // entering the loop: beamShift2 sends only the reconnections outside their beam's free cone through it.
 // (TRI: the occluders in LDS or in global memory -- one loop for the lanes that walk their beam's list and, in LDS, the lanes
 // whose list overflowed: every occluder)
-// the triangles triHit3 left undecided once more, through the crossing point (shift_device.h, triHitFine).  Rare (a few
+// the triangles triHit3 left undecided once more, through the crossing point (occlusion.h, triHitFine).  Rare (a few
 // per cent of the segments that take the loop) and not inlined: inlined, its temporaries cost the evaluation kernel 23 spilled
 // registers.  The new beam's direction is good to ~1e-6 of the reference's, its end point (the offset position) to endErr.
 static __device__ __noinline__ int beamNearRefine(const BeamNearFmt fmt, bool ovf, uint32_t nl0, uint32_t nl1, uint32_t nl2, const float4 *tri,
@@ -756,7 +756,7 @@ static __device__ __noinline__ int beamNearRefine(const BeamNearFmt fmt, bool ov
   }
   return res;
 }
-// (round 5: three states, shift_device.h triHit3 -- MISS, HIT, or AMB: some listed triangle's test lies inside its fp32 margin
+// (round 5: three states, occlusion.h triHit3 -- MISS, HIT, or AMB: some listed triangle's test lies inside its fp32 margin
 // and none is a certain hit; the reconnection then goes to the exact pass)
 __device__ __forceinline__ int beamNearLoop(const GatherArgs &a, const BeamNearFmt fmt, bool ovf, const BeamF &b, const float4 *tri, f3 nd,
                                             float dist) {

@@ -279,7 +279,7 @@ __device__ __forceinline__ void nearVisit(f3 P, const float4 *bvh, const float4 
 // every admissible d: the wall can never be hit and is left out.  With the parent BEHIND the plane, directions within
 // |delta| / Epsilon of grazing meet it at t_self >= Epsilon -- the reference's rayIntersect reports that self-hit
 // (shift_volume_photon.cpp:396-398) -- so the wall STAYS in the list and the evaluation decides (triHitChecked,
-// shift_device.h: fp64 where fp32 cannot tell).  delta's sign is pure rounding noise of the inputs: it is taken in fp64
+// occlusion.h: fp64 where fp32 cannot tell).  delta's sign is pure rounding noise of the inputs: it is taken in fp64
 // from the fp32 data, as the oracle's (and a double-precision reference's) Moeller-Trumbore sees it.
 // cstar (in / out): for a parent BEHIND the plane the wall is left out all the same and its reach is kept instead --
 // max over the parent's own-wall triangles of |delta| / Epsilon, delta the distance to the triangle's plane (unit normal):

@@ -1,6 +1,7 @@
 // C ABI of libgvpm_hip.so (include/gvpm_hip.h): handle, uploads, per-iteration driver.
 // Mirrors the driver logic of GPMIntegrator::photonMapPass / computeVolumeGradientPhotonBRE
 // (gvpm/gvpm.cpp:383-500, 988-1079) and scaleVolumeAPA (gvpm.cpp:181-215).
+#include "bsdf_table.h"
 #include "context.h"
 #include <cfloat>
 
@@ -368,106 +369,91 @@ int gvpm_upload_medium(gvpm_context *h, const gvpm_medium *m) {
   return GVPM_OK;
 }
 
+// The raw entries behind head i (bsdf_table.h): all there, every word valid.
+static int checkBsdfTail(gvpm_context *h, const gvpm_bsdf *table, uint32_t i, uint32_t n, const char *missing, const char *invalid) {
+  const int kind = table[i].kind, tail = gvpm::bsdfTailEntries(kind);
+  if (n - i <= (uint32_t)tail) return fail(h, GVPM_ERR_INVALID_ARG, missing);
+  float raw[16 * GVPM_RTRANS_ENTRIES];  // (the longest tail)
+  memcpy(raw, &table[i + 1], tail * sizeof(gvpm_bsdf));
+  for (int j = 0; j < 16 * tail; ++j)
+    if (!gvpm::bsdfTailWordValid(kind, j, raw[j])) return fail(h, GVPM_ERR_INVALID_ARG, invalid);
+  return GVPM_OK;
+}
+
+// The rules of head i and of what follows it, in the order they are reported.
+static int checkBsdf(gvpm_context *h, const gvpm_bsdf *table, uint32_t i, uint32_t n) {
+  using namespace gvpm;
+  const gvpm_bsdf &b = table[i];
+  const bool weightOk = bsdfWeightValid(b.specular_sampling_weight);
+  const bool ward = b.kind == GVPM_BSDF_WARD || b.kind == GVPM_BSDF_WARD_ANISO;
+  const bool conductor = b.kind == GVPM_BSDF_ROUGHCONDUCTOR || b.kind == GVPM_BSDF_ROUGHCONDUCTOR_ANISO;
+  if (b.kind == GVPM_BSDF_PHONG) {
+    if (!(b.exponent >= 0.f) || !weightOk) return fail(h, GVPM_ERR_INVALID_ARG, "Phong: exponent >= 0 and a sampling weight in [0, 1]");
+  } else if (ward || conductor) {
+    // an anisotropic head has the fields of its isotropic sibling (exponent = alphaU) and ONE raw entry behind it:
+    // {s, alphaV, 0 x 12}
+    const bool aniso = bsdfTailEntries(b.kind) != 0;
+    float alphaV = b.exponent;
+    if (aniso) {
+      if (int rc = checkBsdfTail(h, table, i, n, "anisotropic Ward / rough conductor: the frame entry behind the head is missing",
+                                 "frame entry: tangent and alphaV are +0 or normal floats; 12 zero words behind them"))
+        return rc;
+      float fr[4];
+      memcpy(fr, &table[i + 1], sizeof fr);
+      const double sl = std::sqrt((double)fr[0] * fr[0] + (double)fr[1] * fr[1] + (double)fr[2] * fr[2]);
+      if (!(std::fabs(sl - 1.0) <= 1e-3)) return fail(h, GVPM_ERR_INVALID_ARG, "frame entry: the tangent is a unit vector (to 1e-3)");
+      alphaV = fr[3];
+      // (for Ward, whose plugin has no clamp, this library's own limit)
+      if (!bsdfAlphaValid(b.exponent) || !bsdfAlphaValid(alphaV))
+        return fail(h, GVPM_ERR_INVALID_ARG, "anisotropic Ward / rough conductor: alphaU, alphaV >= 1e-4");
+    } else if (conductor && !bsdfAlphaValid(b.exponent)) {
+      return fail(h, GVPM_ERR_INVALID_ARG, "rough conductor: alpha >= 1e-4 (the reference clamps it)");
+    }
+    if (ward) {
+      // (both components: Ward::sampleComponent picks one below roughness 0.05, ward.cpp:370-389 -- such a surface is outside
+      // the closed set; Ward::getRoughness = 0.5 (alphaU + alphaV), ward.cpp:365: alpha itself for the isotropic kind)
+      if (!(0.5f * (b.exponent + alphaV) >= 0.05f) || !weightOk)
+        return fail(h, GVPM_ERR_INVALID_ARG,
+                    aniso ? "Ward: 0.5 (alphaU + alphaV) >= 0.05 (both components) and a sampling weight in [0, 1]"
+                          : "Ward: alpha >= 0.05 (both components) and a sampling weight in [0, 1]");
+      if (!bsdfWardVariantValid(b)) return fail(h, GVPM_ERR_UNSUPPORTED, "Ward: variant ward / ward-duer / balanced, both components");
+    } else if (!bsdfMicrofacetValid(b)) {
+      return fail(h, GVPM_ERR_UNSUPPORTED, "rough conductor: Beckmann or GGX");
+    }
+  } else if (b.kind == GVPM_BSDF_ROUGHPLASTIC || b.kind == GVPM_BSDF_PLASTIC) {
+    // (include/gvpm_hip.h: eta[0] = eta, eta[1] = Fdr, k[0] = the component met, k[1] = nonlinear)
+    const bool rough = b.kind == GVPM_BSDF_ROUGHPLASTIC;
+    if (rough && !bsdfAlphaValid(b.exponent)) return fail(h, GVPM_ERR_INVALID_ARG, "rough plastic: alpha >= 1e-4 (the reference clamps it)");
+    if (rough && !bsdfMicrofacetValid(b)) return fail(h, GVPM_ERR_UNSUPPORTED, "rough plastic: Beckmann or GGX");
+    if (!(b.eta[0] >= 1.f && b.eta[0] <= FLT_MAX) || !(b.eta[1] >= 0.f && b.eta[1] < 1.f) || !weightOk)
+      return fail(h, GVPM_ERR_INVALID_ARG, "plastic: eta >= 1 and finite, Fdr in [0, 1), a sampling weight in [0, 1]");
+    if (rough ? !(b.k[0] == 0.f || b.k[0] == 1.f || b.k[0] == 2.f) : b.k[0] != 2.f)
+      return fail(h, GVPM_ERR_INVALID_ARG, "plastic: component 0 / 1 / 2 (rough plastic), 2 = the diffuse one (plastic)");
+    if (b.k[1] != 0.f && b.k[1] != 1.f) return fail(h, GVPM_ERR_INVALID_ARG, "plastic: nonlinear is 0 or 1");
+    // the slice: raw entries behind the head, copied as they are
+    if (rough)
+      return checkBsdfTail(h, table, i, n, "rough plastic: the 7 entries of the transmittance slice are missing",
+                           "rough plastic: slice values are finite, in [0, 1] and not subnormal; 12 zero words behind them");
+  } else {
+    return fail(h, GVPM_ERR_UNSUPPORTED,
+                "bsdf kind outside the device's closed set (Phong, rough conductor, Ward, the plastics, anisotropic Ward / rough conductor)");
+  }
+  return GVPM_OK;
+}
+
 int gvpm_upload_bsdfs(gvpm_context *h, const gvpm_bsdf *table, uint32_t n) {
   CHECK_H(h);
   if (int rcj = gvpm_join_exact(h)) return rcj;  // (deferred shifts are evaluated against the scene they met)
   if (n && !table) return fail(h, GVPM_ERR_INVALID_ARG, "null bsdf table");
   if (n > (1u << 24)) return fail(h, GVPM_ERR_INVALID_ARG, "more than 2^24 bsdfs (the index travels as a float)");
-  // four quads per entry: {kind, specular} {exponent | alpha, sampling weight, distribution, sample_visible} {eta, k.x} {k.yz}
+  // four quads per entry (bsdf_table.h); the raw entries behind a head travel as they are
   std::vector<float4> rows(4 * (size_t)n + 4);
   for (uint32_t i = 0; i < n; ++i) {
-    const gvpm_bsdf &b = table[i];
-    float kindBits, distBits, visBits;
-    memcpy(&kindBits, &b.kind, 4);
-    memcpy(&distBits, &b.distribution, 4);
-    memcpy(&visBits, &b.sample_visible, 4);
-    if (b.kind == GVPM_BSDF_PHONG) {
-      if (!(b.exponent >= 0.f) || !(b.specular_sampling_weight >= 0.f && b.specular_sampling_weight <= 1.f))
-        return fail(h, GVPM_ERR_INVALID_ARG, "Phong: exponent >= 0 and a sampling weight in [0, 1]");
-    } else if (b.kind == GVPM_BSDF_ROUGHCONDUCTOR) {
-      if (!(b.exponent >= 1e-4f)) return fail(h, GVPM_ERR_INVALID_ARG, "rough conductor: alpha >= 1e-4 (the reference clamps it)");
-      if (b.distribution != GVPM_MICROFACET_BECKMANN && b.distribution != GVPM_MICROFACET_GGX)
-        return fail(h, GVPM_ERR_UNSUPPORTED, "rough conductor: Beckmann or GGX");
-    } else if (b.kind == GVPM_BSDF_WARD) {
-      // (both components: Ward::sampleComponent picks one below roughness 0.05, ward.cpp:370-389 -- such a surface is outside
-      // the closed set; isotropic by construction: the entry has one alpha)
-      if (!(b.exponent >= 0.05f) || !(b.specular_sampling_weight >= 0.f && b.specular_sampling_weight <= 1.f))
-        return fail(h, GVPM_ERR_INVALID_ARG, "Ward: alpha >= 0.05 (both components) and a sampling weight in [0, 1]");
-      if (b.sample_visible < GVPM_WARD_WARD || b.sample_visible > GVPM_WARD_BALANCED || b.distribution != 0)
-        return fail(h, GVPM_ERR_UNSUPPORTED, "Ward: variant ward / ward-duer / balanced, both components");
-    } else if (b.kind == GVPM_BSDF_ROUGHPLASTIC || b.kind == GVPM_BSDF_PLASTIC) {
-      // (include/gvpm_hip.h: eta[0] = eta, eta[1] = Fdr, k[0] = the component met, k[1] = nonlinear)
-      const bool rough = b.kind == GVPM_BSDF_ROUGHPLASTIC;
-      if (rough && !(b.exponent >= 1e-4f)) return fail(h, GVPM_ERR_INVALID_ARG, "rough plastic: alpha >= 1e-4 (the reference clamps it)");
-      if (rough && b.distribution != GVPM_MICROFACET_BECKMANN && b.distribution != GVPM_MICROFACET_GGX)
-        return fail(h, GVPM_ERR_UNSUPPORTED, "rough plastic: Beckmann or GGX");
-      if (!(b.eta[0] >= 1.f && b.eta[0] <= FLT_MAX) || !(b.eta[1] >= 0.f && b.eta[1] < 1.f) ||
-          !(b.specular_sampling_weight >= 0.f && b.specular_sampling_weight <= 1.f))
-        return fail(h, GVPM_ERR_INVALID_ARG, "plastic: eta >= 1 and finite, Fdr in [0, 1), a sampling weight in [0, 1]");
-      if (rough ? !(b.k[0] == 0.f || b.k[0] == 1.f || b.k[0] == 2.f) : b.k[0] != 2.f)
-        return fail(h, GVPM_ERR_INVALID_ARG, "plastic: component 0 / 1 / 2 (rough plastic), 2 = the diffuse one (plastic)");
-      if (b.k[1] != 0.f && b.k[1] != 1.f) return fail(h, GVPM_ERR_INVALID_ARG, "plastic: nonlinear is 0 or 1");
-      if (rough) {
-        // the slice: GVPM_RTRANS_ENTRIES raw entries behind the head, copied as they are
-        if (n - i <= (uint32_t)GVPM_RTRANS_ENTRIES)
-          return fail(h, GVPM_ERR_INVALID_ARG, "rough plastic: the 7 entries of the transmittance slice are missing");
-        float raw[16 * GVPM_RTRANS_ENTRIES];
-        memcpy(raw, &table[i + 1], sizeof raw);
-        for (int j = 0; j < 16 * GVPM_RTRANS_ENTRIES; ++j) {
-          // (zero or a NORMAL float: a raw entry's first word must never read as a kind)
-          const bool okv = j < GVPM_RTRANS_KNOTS ? (raw[j] == 0.f || (raw[j] >= FLT_MIN && raw[j] <= 1.f)) : raw[j] == 0.f;
-          uint32_t bits;
-          memcpy(&bits, &raw[j], 4);
-          if (!okv || bits == 0x80000000u)
-            return fail(h, GVPM_ERR_INVALID_ARG, "rough plastic: slice values are finite, in [0, 1] and not subnormal; 12 zero words behind them");
-        }
-      }
-    } else if (b.kind == GVPM_BSDF_WARD_ANISO || b.kind == GVPM_BSDF_ROUGHCONDUCTOR_ANISO) {
-      // a head with the fields of its isotropic sibling (exponent = alphaU) and ONE raw entry behind it: {s, alphaV, 0 x 12}
-      const bool ward = b.kind == GVPM_BSDF_WARD_ANISO;
-      if (n - i <= (uint32_t)GVPM_ANISO_ENTRIES)
-        return fail(h, GVPM_ERR_INVALID_ARG, "anisotropic Ward / rough conductor: the frame entry behind the head is missing");
-      float raw[16 * GVPM_ANISO_ENTRIES];
-      memcpy(raw, &table[i + 1], sizeof raw);
-      for (int j = 0; j < 16 * GVPM_ANISO_ENTRIES; ++j) {
-        // (+0 or a NORMAL float: a raw entry's first word must never read as a kind)
-        uint32_t bits;
-        memcpy(&bits, &raw[j], 4);
-        const bool okv = j < 4 ? (bits == 0u || (fabsf(raw[j]) >= FLT_MIN && fabsf(raw[j]) <= FLT_MAX)) : bits == 0u;
-        if (!okv)
-          return fail(h, GVPM_ERR_INVALID_ARG, "frame entry: tangent and alphaV are +0 or normal floats; 12 zero words behind them");
-      }
-      const double sl = std::sqrt((double)raw[0] * raw[0] + (double)raw[1] * raw[1] + (double)raw[2] * raw[2]);
-      if (!(std::fabs(sl - 1.0) <= 1e-3)) return fail(h, GVPM_ERR_INVALID_ARG, "frame entry: the tangent is a unit vector (to 1e-3)");
-      const float alphaV = raw[3];
-      // (alpha >= 1e-4: the microfacet constructor's clamp, microfacet.h:88-90; for Ward this library's own limit)
-      if (!(b.exponent >= 1e-4f) || !(alphaV >= 1e-4f))
-        return fail(h, GVPM_ERR_INVALID_ARG, "anisotropic Ward / rough conductor: alphaU, alphaV >= 1e-4");
-      if (ward) {
-        // (both components: Ward::getRoughness = 0.5 (alphaU + alphaV), ward.cpp:365, against sampleComponent, :370-389)
-        if (!(0.5f * (b.exponent + alphaV) >= 0.05f) || !(b.specular_sampling_weight >= 0.f && b.specular_sampling_weight <= 1.f))
-          return fail(h, GVPM_ERR_INVALID_ARG, "Ward: 0.5 (alphaU + alphaV) >= 0.05 (both components) and a sampling weight in [0, 1]");
-        if (b.sample_visible < GVPM_WARD_WARD || b.sample_visible > GVPM_WARD_BALANCED || b.distribution != 0)
-          return fail(h, GVPM_ERR_UNSUPPORTED, "Ward: variant ward / ward-duer / balanced, both components");
-      } else if (b.distribution != GVPM_MICROFACET_BECKMANN && b.distribution != GVPM_MICROFACET_GGX) {
-        return fail(h, GVPM_ERR_UNSUPPORTED, "rough conductor: Beckmann or GGX");
-      }
-    } else {
-      return fail(h, GVPM_ERR_UNSUPPORTED,
-                  "bsdf kind outside the device's closed set (Phong, rough conductor, Ward, the plastics, anisotropic Ward / rough conductor)");
-    }
-    rows[4 * i] = make_float4(kindBits, b.specular[0], b.specular[1], b.specular[2]);
-    rows[4 * i + 1] = make_float4(b.exponent, b.specular_sampling_weight, distBits, visBits);
-    rows[4 * i + 2] = make_float4(b.eta[0], b.eta[1], b.eta[2], b.k[0]);
-    rows[4 * i + 3] = make_float4(b.k[1], b.k[2], 0.f, 0.f);
-    if (b.kind == GVPM_BSDF_ROUGHPLASTIC) {
-      memcpy(&rows[4 * (size_t)i + 4], &table[i + 1], GVPM_RTRANS_ENTRIES * sizeof(gvpm_bsdf));
-      i += GVPM_RTRANS_ENTRIES;
-    }
-    if (b.kind == GVPM_BSDF_WARD_ANISO || b.kind == GVPM_BSDF_ROUGHCONDUCTOR_ANISO) {
-      memcpy(&rows[4 * (size_t)i + 4], &table[i + 1], GVPM_ANISO_ENTRIES * sizeof(gvpm_bsdf));
-      i += GVPM_ANISO_ENTRIES;
-    }
+    if (int rc = checkBsdf(h, table, i, n)) return rc;
+    const int tail = gvpm::bsdfTailEntries(table[i].kind);
+    gvpm::bsdfPackRows(table[i], &rows[4 * (size_t)i].x);
+    memcpy(&rows[4 * (size_t)i + 4], &table[i + 1], tail * sizeof(gvpm_bsdf));
+    i += tail;
   }
   // once per scene: waits for whatever still reads the old table (as gvpm_upload_materials does)
   HIP_TRY(h, hipStreamSynchronize(h->stream));

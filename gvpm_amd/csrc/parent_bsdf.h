@@ -1,0 +1,284 @@
+// The BSDF models of a glossy surface parent (GVPM_PARENT_SURFACE_BSDF): microfacet distributions, Fresnel terms, the rough
+// transmittance and the evaluation of one entry of the table of gvpm_upload_bsdfs, whose rows bsdf_table.h lays out.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "bsdf_table.h"
+#include "device_types.h"
+#include "vec.h"
+
+namespace gvpm {
+
+#define PI_F 3.14159265358979323846f
+#define INV_PI_F 0.31830988618379067154f
+#define INV_TWOPI_F 0.15915494309189533577f
+#define INV_FOURPI_F 0.07957747154594766788f
+
+// MicrofacetDistribution, isotropic (src/bsdfs/microfacet.h): D of a half vector with cosine cH to the normal (:191-232) and
+// Smith's G1 of a direction with cosine cV to the normal and vDotH to the half vector (:477-518).
+__device__ __forceinline__ float microfacetD(int ggx, float alpha, float cH) {
+  if (cH <= 0.f) return 0.f;
+  const float c2 = cH * cH;
+  const float e = fdiv(fmaxf(1.f - c2, 0.f), alpha * alpha * c2);  // tan^2 / alpha^2
+  float r;
+  if (ggx) {
+    const float root = (1.f + e) * c2;
+    r = frcp(PI_F * alpha * alpha * root * root);
+  } else {
+    r = fdiv(__expf(-e), PI_F * alpha * alpha * c2 * c2);
+  }
+  return r * cH < 1e-20f ? 0.f : r;
+}
+__device__ __forceinline__ float microfacetG1(int ggx, float alpha, float cV, float vDotH) {
+  if (vDotH * cV <= 0.f) return 0.f;
+  const float t2 = 1.f - cV * cV;
+  if (t2 <= 0.f) return 1.f;  // perpendicular incidence
+  const float tanT = fabsf(fdiv(fsqrt(t2), cV));
+  if (ggx) {
+    const float root = alpha * tanT;
+    return fdiv(2.f, 1.f + fsqrt(1.f + root * root));
+  }
+  const float a = frcp(alpha * tanT);
+  if (a >= 1.6f) return 1.f;
+  const float a2 = a * a;
+  return fdiv(3.535f * a + 2.181f * a2, 1.f + 2.276f * a + 2.577f * a2);
+}
+// The anisotropic kinds (GVPM_BSDF_WARD_ANISO, GVPM_BSDF_ROUGHCONDUCTOR_ANISO): the frame entry behind the head carries the
+// surface's tangent s and alphaV; with the record's parent normal n, s' = normalize(s - n (n . s)) and t = n x s' stand for the
+// shading frame's s and t.  Only SQUARES of the tangential components enter the formulas, so neither the sign of s nor the
+// handedness of (s', t, n) matters.  False: the tangent is parallel to the normal -- a failed shift.
+__device__ __forceinline__ bool anisoFrame(const float4 fr, f3 n, f3 &s, f3 &t) {
+  s = mk3(fr.x, fr.y, fr.z);
+  s = s - n * dot(n, s);
+  const float ss = dot(s, s);
+  if (ss < 1e-12f) return false;
+  s = s * frsq(ss);
+  t = cross(n, s);
+  return true;
+}
+// MicrofacetDistribution::eval with alphaU != alphaV (microfacet.h:191-232): mx, my, cH = the unit half vector in the frame
+__device__ __forceinline__ float microfacetDAniso(int ggx, float au, float av, float mx, float my, float cH) {
+  if (cH <= 0.f) return 0.f;
+  const float c2 = cH * cH, ux = fdiv(mx, au), uy = fdiv(my, av);
+  const float e = fdiv(ux * ux + uy * uy, c2);
+  float r;
+  if (ggx) {
+    const float root = (1.f + e) * c2;
+    r = frcp(PI_F * au * av * root * root);
+  } else {
+    r = fdiv(__expf(-e), PI_F * au * av * c2 * c2);
+  }
+  return r * cH < 1e-20f ? 0.f : r;
+}
+// projectRoughness (microfacet.h:541-551) of a unit direction with tangential components vx, vy and cosine cV; at
+// perpendicular incidence (sin^2 <= 0) the value is not used: microfacetG1 returns 1 before it reads alpha (:484-488)
+__device__ __forceinline__ float projectRoughness(float au, float av, float vx, float vy, float cV) {
+  return fsqrt(fdiv(vx * vx * (au * au) + vy * vy * (av * av), 1.f - cV * cV));
+}
+// fresnelConductorExact, one channel (src/libcore/util.cpp:747-769)
+__device__ __forceinline__ float fresnelConductor(float cI, float eta, float k) {
+  const float c2 = cI * cI, s2 = 1.f - c2, s4 = s2 * s2;
+  const float t1 = eta * eta - k * k - s2;
+  const float a2pb2 = fsqrt(fmaxf(t1 * t1 + k * k * eta * eta * 4.f, 0.f));
+  const float aa = fsqrt(fmaxf((a2pb2 + t1) * 0.5f, 0.f));
+  const float term1 = a2pb2 + c2, term2 = aa * (2.f * cI);
+  const float Rs2 = fdiv(term1 - term2, term1 + term2);
+  const float term3 = a2pb2 * c2 + s4, term4 = term2 * s2;
+  const float Rp2 = Rs2 * fdiv(term3 - term4, term3 + term4);
+  return 0.5f * (Rp2 + Rs2);
+}
+// fresnelDielectricExt for a cosine >= 0 and eta >= 1 (src/libcore/util.cpp:659-689): exactly 0 at eta == 1; no total internal
+// reflection from the rarer side
+__device__ __forceinline__ float fresnelDielectric(float cI, float eta) {
+  if (eta == 1.f) return 0.f;
+  const float ie = frcp(eta);
+  const float cT = fsqrt(fmaxf(1.f - (1.f - cI * cI) * (ie * ie), 0.f));
+  const float Rs = fdiv(cI - eta * cT, cI + eta * cT), Rp = fdiv(eta * cI - cT, eta * cI + cT);
+  return 0.5f * (Rs * Rs + Rp * Rp);
+}
+// RoughTransmittance::eval with eta and alpha fixed (src/bsdfs/rtrans.h:183-236): evalCubicInterp1D (libcore/spline.cpp:23-60)
+// of the 100 values `t` over cos^(1/4) in [0, 1] -- Catmull-Rom, one-sided differences at the ends, left knot
+// min(floor(x), 98) -- clamped to [0, 1].  c > 0 is the caller's test; a cosine that rounding left above 1 is looked up at 1.
+__device__ __forceinline__ float roughTransmittance(const float *__restrict__ t, float c) {
+  const float x = fsqrt(fsqrt(fminf(c, 1.f))) * (float)(GVPM_RTRANS_KNOTS - 1);
+  const int k = min((int)x, GVPM_RTRANS_KNOTS - 2);
+  const float f0 = t[k], f1 = t[k + 1];
+  const float fm = t[max(k - 1, 0)], f2 = t[min(k + 2, GVPM_RTRANS_KNOTS - 1)];
+  const float d0 = k > 0 ? 0.5f * (f1 - fm) : f1 - f0;
+  const float d1 = k + 2 < GVPM_RTRANS_KNOTS ? 0.5f * (f2 - f0) : f1 - f0;
+  const float u = x - (float)k, u2 = u * u, u3 = u2 * u;
+  const float r = (2.f * u3 - 3.f * u2 + 1.f) * f0 + (-2.f * u3 + 3.f * u2) * f1 + (u3 - 2.f * u2 + u) * d0 + (u3 - u2) * d1;
+  return fminf(fmaxf(r, 0.f), 1.f);
+}
+
+// a head's specular reflectance (bsdf_table.h, row 0)
+__device__ __forceinline__ f3 bsdfSpecular3(const float4 b0) { return mk3(bsdfSpecular<0>(b0), bsdfSpecular<1>(b0), bsdfSpecular<2>(b0)); }
+
+// A glossy surface parent (GVPM_PARENT_SURFACE_BSDF): BSDF::eval and BSDF::pdf * pdfComponent of the table entry the
+// record names, towards the new direction `wo` (shift_diffuse.cpp:25-41 with bRec.component = -1).  Phong, src/bsdfs/
+// phong.cpp:121-186: eval = (ks (e + 2) / 2pi alpha^e + kd / pi) cos_o, pdf = w alpha^e (e + 1) / 2pi + (1 - w) cos_o / pi,
+// alpha = wo . reflect(wi).  Rough conductor, src/bsdfs/roughconductor.cpp:257-319: eval = F D G / (4 cos_i), pdf = D G1(wi)
+// / (4 cos_i) or D cos_H / (4 |wo . H|) (include/gvpm_hip.h).  cosWi, cosWo > 0 is the caller's test.  False: no such
+// entry (a failed shift).
+// state (optional out, round 5): bit 0 -- the pdf is POSITIVE in double precision although it underflowed here (the
+// specular component of a Phong wall alone, exponent ~1000: alpha^e leaves fp32 below alpha ~ 0.94 and fp64 only below ~0.6;
+// with pdf == 0 the reference fails the shift, with a positive one -- however small -- it succeeds, with weight 1 and a
+// flux that rounds to zero: only the counter tells them apart); bit 1 -- within rounding of the double's own underflow:
+// the exact pass decides, with the lobe in fp64 (phongEvalD).
+__device__ __forceinline__ bool glossyParentEval(const GatherArgs &a, float index, f3 kd, f3 n, f3 wi, f3 wo, float cosWi,
+                                                 float cosWo, f3 &f, float &pdf, uint32_t *state = nullptr) {
+  const uint32_t bi = (uint32_t)index;
+  f = mk3(0.f);
+  pdf = 0.f;
+  if (state) *state = 0u;
+  if (!(index >= 0.f) || bi >= a.nbsdfs) return false;
+  const float4 b0 = a.bsdfs[4 * bi], b1 = a.bsdfs[4 * bi + 1];
+  const int kind = bsdfKind(b0);
+  if (kind == GVPM_BSDF_PHONG) {
+    // (the sampling weight is read as the lane it is: through bsdfSamplingWeight the compiler swaps the operands of a mask
+    // `and` in the G-VPM kernels, and this change leaves every instruction where it was -- NOTEBOOK.md)
+    const float e = bsdfExponent(b1), w = b1.y;
+    const f3 refl = n * (2.f * cosWi) - wi;
+    const float alpha = dot(wo, refl);
+    const float l2 = alpha > 0.f ? e * __builtin_log2f(alpha) : -INFINITY;
+    float lobe = alpha > 0.f ? __builtin_exp2f(l2) : 0.f;  // std::pow(alpha, exponent)
+    // (the entry's component: 0 both, 1 the specular lobe alone, 2 the diffuse one alone -- bRec.component + 1; a component's
+    // pdf times its pdfComponent IS its term of the mixture, phong.cpp:157-186,331-342)
+    const int comp = bsdfPhongComponent(b1);
+    const float dOn = comp == 1 ? 0.f : 1.f;
+    if (comp == 2) lobe = 0.f;
+    f = (bsdfSpecular3(b0) * ((e + 2.f) * INV_TWOPI_F * lobe) + kd * (INV_PI_F * dOn)) * cosWo;
+    pdf = w * (lobe * (e + 1.f) * INV_TWOPI_F) + (1.f - w) * (INV_PI_F * cosWo * dOn);
+    if (state && comp == 1 && pdf == 0.f && w > 0.f) {
+      // the double's lobe is zero below 2^-1074; the factors beside it (w (e + 1) / 2 pi, 1 / l^2, the medium's pdf) move the
+      // product's own underflow by a few tens of binades: a band of +-64 around it, and |alpha| within rounding of zero
+      *state = (l2 > -1010.f ? 1u : 0u) | ((l2 > -1138.f && l2 <= -1010.f) || fabsf(alpha) <= 1e-6f ? 2u : 0u);
+    }
+    return true;
+  }
+  if (kind == GVPM_BSDF_WARD || kind == GVPM_BSDF_WARD_ANISO) {
+    // src/bsdfs/ward.cpp:178-266, both components (roughness >= 0.05); H NOT normalised in eval, as the reference has it; the
+    // variant rides in the field the rough conductor uses for its pdf's form.  Isotropic: alphaU == alphaV = the head's alpha.
+    // Anisotropic: alphaU = the head's alpha, alphaV and the tangent in the frame entry behind the head; alphaU alphaV stands where
+    // alpha^2 stood, and the exponent -((H.x / alphaU)^2 + (H.y / alphaV)^2) / H.z^2 is scale-free in H: eval and pdf share it
+    const float w = bsdfSamplingWeight(b1);
+    const int variant = bsdfWardVariant(b1);
+    const f3 H = wi + wo;
+    const float HH = dot(H, H), Hz = cosWi + cosWo;
+    float ia2, ex;
+    if (kind == GVPM_BSDF_WARD) {
+      ia2 = frcp(bsdfAlpha(b1) * bsdfAlpha(b1));
+      ex = -(HH - Hz * Hz) * frcp(Hz * Hz) * ia2;
+    } else {
+      const float4 fr = a.bsdfs[4 * (bi + 1)];
+      f3 s, t;
+      if (!anisoFrame(fr, n, s, t)) return false;
+      const float ux = fdiv(dot(H, s), bsdfAlpha(b1)), uy = fdiv(dot(H, t), bsdfFrameAlphaV(fr));
+      ia2 = frcp(bsdfAlpha(b1) * bsdfFrameAlphaV(fr));
+      ex = -(ux * ux + uy * uy) * frcp(Hz * Hz);
+    }
+    const float E = __expf(ex);
+    float factor1;
+    if (variant == GVPM_WARD_WARD) factor1 = INV_FOURPI_F * ia2 * frsq(cosWi * cosWo);
+    else if (variant == GVPM_WARD_DUER) factor1 = INV_FOURPI_F * ia2 * frcp(cosWi * cosWo);
+    else factor1 = HH * INV_PI_F * ia2 * frcp(Hz * Hz * Hz * Hz);
+    const float specRef = factor1 * E;
+    f = (bsdfSpecular3(b0) * (specRef > 1e-10f ? specRef : 0.f) + kd * INV_PI_F) * cosWo;
+    // pdf: the normalised half vector; Hn . wi = (1 + wi . wo) / |H|, cos(theta_Hn) = Hz / |H|
+    const float iH = frsq(HH), cH = Hz * iH, wiH = dot(wi, H) * iH;
+    pdf = w * (INV_FOURPI_F * ia2 * E * frcp(wiH * cH * cH * cH)) + (1.f - w) * (INV_PI_F * cosWo);
+    return true;
+  }
+  if (kind == GVPM_BSDF_ROUGHCONDUCTOR || kind == GVPM_BSDF_ROUGHCONDUCTOR_ANISO) {
+    const float4 b2 = a.bsdfs[4 * bi + 2], b3 = a.bsdfs[4 * bi + 3];
+    const float alpha = bsdfAlpha(b1);
+    const int ggx = bsdfDistribution(b1) == GVPM_MICROFACET_GGX, vis = bsdfSampleVisible(b1) != 0;
+    f3 H = wi + wo;
+    H = H * frsq(dot(H, H));
+    const float cH = dot(H, n), wiH = dot(wi, H), woH = dot(wo, H);
+    float D, alI = alpha, alO = alpha;  // (anisotropic: alphaU = the head's alpha, the roughness projected on wi and on wo)
+    if (kind == GVPM_BSDF_ROUGHCONDUCTOR) {
+      D = microfacetD(ggx, alpha, cH);
+    } else {
+      const float4 fr = a.bsdfs[4 * (bi + 1)];
+      f3 s, t;
+      if (!anisoFrame(fr, n, s, t)) return false;
+      D = microfacetDAniso(ggx, alpha, bsdfFrameAlphaV(fr), dot(H, s), dot(H, t), cH);
+      if (D != 0.f) {
+        alI = projectRoughness(alpha, bsdfFrameAlphaV(fr), dot(wi, s), dot(wi, t), cosWi);
+        alO = projectRoughness(alpha, bsdfFrameAlphaV(fr), dot(wo, s), dot(wo, t), cosWo);
+      }
+    }
+    if (D == 0.f) return true;  // eval and pdf both zero (pdfAll = D cos_H, pdfVisible = D G1 ...)
+    const float G1i = microfacetG1(ggx, alI, cosWi, wiH), G1o = microfacetG1(ggx, alO, cosWo, woH);
+    const float model = fdiv(D * G1i * G1o, 4.f * cosWi);
+    f = mk3(fresnelConductor(wiH, bsdfConductorEta<0>(b2), bsdfConductorK<0>(b2, b3)) * bsdfSpecular<0>(b0),
+            fresnelConductor(wiH, bsdfConductorEta<1>(b2), bsdfConductorK<1>(b2, b3)) * bsdfSpecular<1>(b0),
+            fresnelConductor(wiH, bsdfConductorEta<2>(b2), bsdfConductorK<2>(b2, b3)) * bsdfSpecular<2>(b0)) * model;
+    pdf = vis ? fdiv(D * G1i, 4.f * cosWi) : fdiv(D * cH, 4.f * fabsf(woH));
+    return true;
+  }
+  if (kind == GVPM_BSDF_ROUGHPLASTIC || kind == GVPM_BSDF_PLASTIC) {
+    // src/bsdfs/roughplastic.cpp:326-437,566-586 and the diffuse component of src/bsdfs/plastic.cpp:245-307,451-477
+    // (include/gvpm_hip.h): row 2 = {eta, Fdr, -, component met}, row 3 = {nonlinear, ...}; a rough-plastic head is followed by
+    // its transmittance slice, 100 contiguous floats (gvpm_upload_bsdfs checked that they are there)
+    const float4 b2 = a.bsdfs[4 * bi + 2], b3 = a.bsdfs[4 * bi + 3];
+    const float w = bsdfSamplingWeight(b1), eta = bsdfPlasticEta(b2), Fdr = bsdfPlasticFdr(b2);
+    const int comp = (int)bsdfPlasticComponent(b2);  // 0 both, 1 the glossy component alone, 2 the diffuse one alone
+    float Ti, To, spec = 0.f, pdfM = 0.f;
+    if (kind == GVPM_BSDF_ROUGHPLASTIC) {
+      const float *slice = reinterpret_cast<const float *>(a.bsdfs + 4 * (bi + 1));
+      Ti = roughTransmittance(slice, cosWi);
+      To = roughTransmittance(slice, cosWo);
+      const float alpha = bsdfAlpha(b1);
+      const int ggx = bsdfDistribution(b1) == GVPM_MICROFACET_GGX, vis = bsdfSampleVisible(b1) != 0;
+      f3 H = wi + wo;
+      H = H * frsq(dot(H, H));
+      const float cH = dot(H, n), wiH = dot(wi, H), woH = dot(wo, H);
+      const float D = microfacetD(ggx, alpha, cH);
+      if (D != 0.f && comp != 2) {
+        const float G1i = microfacetG1(ggx, alpha, cosWi, wiH), G1o = microfacetG1(ggx, alpha, cosWo, woH);
+        spec = fresnelDielectric(wiH, eta) * fdiv(D * G1i * G1o, 4.f * cosWi);
+        pdfM = vis ? fdiv(D * G1i, 4.f * cosWi) : fdiv(D * cH, 4.f * fabsf(woH));
+      }
+    } else {
+      Ti = 1.f - fresnelDielectric(cosWi, eta);
+      To = 1.f - fresnelDielectric(cosWo, eta);
+    }
+    // the probability of the glossy component: 0 / 0 (T = 0 with w = 0, T = 1 with w = 1) is NaN in the reference -- a failed shift
+    const float p = 1.f - Ti, den = p * w + (1.f - p) * (1.f - w);
+    if (!(den > 0.f)) return false;
+    const float pS = fdiv(p * w, den);
+    const float dOn = comp == 1 ? 0.f : 1.f;
+    const bool nl = bsdfPlasticNonlinear(b3);  // kd / (1 - kd Fdr) per channel, else kd / (1 - Fdr)
+    const f3 kdp = mk3(fdiv(kd.x, 1.f - (nl ? kd.x : 1.f) * Fdr), fdiv(kd.y, 1.f - (nl ? kd.y : 1.f) * Fdr),
+                       fdiv(kd.z, 1.f - (nl ? kd.z : 1.f) * Fdr));
+    const float ie = frcp(eta);
+    f = bsdfSpecular3(b0) * spec + kdp * (INV_PI_F * cosWo * Ti * To * (ie * ie) * dOn);
+    pdf = pS * pdfM + (1.f - pS) * (INV_PI_F * cosWo * dOn);
+    return true;
+  }
+  return false;
+}
+
+// Phong::eval (x cos) and Phong::pdf x pdfComponent of a table entry in fp64 (phong.cpp:121-186,331-342): what the exact
+// passes and the fp64 transcription of G-Beams evaluate a Phong parent with -- a lobe of exponent ~1000 lives where fp32 has
+// no numbers.  False: not a Phong entry.
+__device__ __forceinline__ bool phongEvalD(const GatherArgs &a, float index, d3 kd, d3 n, d3 wi, d3 wo, double cosWi, double cosWo,
+                                           d3 &f, double &pdf) {
+  const uint32_t bi = (uint32_t)index;
+  if (!(index >= 0.f) || bi >= a.nbsdfs) return false;
+  const float4 b0 = a.bsdfs[4 * bi], b1 = a.bsdfs[4 * bi + 1];
+  if (bsdfKind(b0) != GVPM_BSDF_PHONG) return false;
+  const double INV_PI = 0.31830988618379067154, INV_TWOPI = 0.15915494309189533577;
+  const double e = bsdfExponent(b1), w = bsdfSamplingWeight(b1);
+  const int comp = bsdfPhongComponent(b1);  // 0 both, 1 specular only, 2 diffuse only (gvpm_hip.h, gvpm_bsdf)
+  const d3 refl = n * (2.0 * cosWi) - wi;
+  const double alpha = dot(wo, refl);
+  const double lobe = (alpha > 0 && comp != 2) ? pow(alpha, e) : 0.0, dOn = comp == 1 ? 0.0 : 1.0;
+  f = (mkd(bsdfSpecular<0>(b0), bsdfSpecular<1>(b0), bsdfSpecular<2>(b0)) * ((e + 2.0) * INV_TWOPI * lobe) + kd * (INV_PI * dOn)) * cosWo;
+  pdf = w * (lobe * (e + 1.0) * INV_TWOPI) + (1.0 - w) * (INV_PI * cosWo * dOn);
+  return true;
+}
+
+}  // namespace gvpm

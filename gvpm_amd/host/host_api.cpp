@@ -1,6 +1,5 @@
 #include "host_api.h"
 
-#include <cfloat>
 #include <cmath>
 #include <vector>
 
@@ -194,85 +193,52 @@ int gvpm_synth_sample_aniso(const gvpm_synth *s, int mat, const double *n, const
   return 1;
 }
 
+// One head of material `m` (`component`: the one it is met through + 1 where an entry per component exists, else 0) and the raw
+// entries behind it (bsdf_table.h); `b` points at 1 + bsdfTailEntries(kind) zeroed entries.
+static void fillBsdf(const gvpm::SynthMat &m, int kind, int component, gvpm_bsdf *b) {
+  const bool ward = kind == GVPM_BSDF_WARD || kind == GVPM_BSDF_WARD_ANISO;
+  const bool conductor = kind == GVPM_BSDF_ROUGHCONDUCTOR || kind == GVPM_BSDF_ROUGHCONDUCTOR_ANISO;
+  b->kind = kind;
+  b->specular[0] = (float)m.spec.x; b->specular[1] = (float)m.spec.y; b->specular[2] = (float)m.spec.z;
+  b->exponent = (float)m.exponent;
+  if (!conductor) b->specular_sampling_weight = (float)m.specWeight;
+  // (sample_visible stays 0 for the microfacet kinds: the host walk samples all normals, synth_core.h)
+  if (kind == GVPM_BSDF_PHONG) b->distribution = component;  // (sampled component + 1; 0: both components, include/gvpm_hip.h)
+  else if (ward) b->sample_visible = m.distribution;         // (the model variant, include/gvpm_hip.h)
+  else if (kind != GVPM_BSDF_PLASTIC) b->distribution = m.distribution;
+  if (conductor) {
+    b->eta[0] = (float)m.eta.x; b->eta[1] = (float)m.eta.y; b->eta[2] = (float)m.eta.z;
+    b->k[0] = (float)m.k.x; b->k[1] = (float)m.k.y; b->k[2] = (float)m.k.z;
+  } else if (kind == GVPM_BSDF_ROUGHPLASTIC || kind == GVPM_BSDF_PLASTIC) {
+    b->eta[0] = (float)m.coatEta;
+    b->eta[1] = (float)m.fdr;
+    b->k[0] = kind == GVPM_BSDF_PLASTIC ? 2.f : (float)component;
+    b->k[1] = (float)m.nonlinear;
+  }
+  if (kind == GVPM_BSDF_ROUGHPLASTIC) {
+    if (m.rtrans) memcpy(b + 1, m.rtrans, GVPM_RTRANS_KNOTS * sizeof(float));
+  } else if (gvpm::bsdfTailEntries(kind)) {
+    // the frame entry {tangent, alphaV, 0 x 12}; a word gvpm_upload_bsdfs would refuse (one that rounds below FLT_MIN) becomes +0
+    float frame[4] = {(float)m.tangent.x, (float)m.tangent.y, (float)m.tangent.z, (float)m.alphaV};
+    for (float &v : frame)
+      if (!gvpm::bsdfRawWordValid(v)) v = 0.f;
+    memcpy(b + 1, frame, sizeof frame);
+  }
+}
+
 uint32_t gvpm_synth_bsdfs(const gvpm_synth *s, gvpm_bsdf *out, uint32_t cap) {
   if (!s) return 0;
   uint32_t n = 0;
   for (const auto &m : s->scene.mats) {
-    const int entries = gvpm::bsdfEntries(m.kind, m.exponent);
-    if (m.kind == gvpm::MAT_ROUGHPLASTIC || m.kind == gvpm::MAT_PLASTIC) {
-      // a head per component met (below alpha 0.05: glossy alone, diffuse alone); a rough head is followed by its slice
-      const int stride = m.kind == gvpm::MAT_ROUGHPLASTIC ? 1 + GVPM_RTRANS_ENTRIES : 1;
-      for (int c = 0; c < entries; ++c) {
-        if (out && (uint32_t)(m.bsdf + (c + 1) * stride) <= cap) {
-          gvpm_bsdf *b = &out[m.bsdf + c * stride];
-          memset(b, 0, stride * sizeof(gvpm_bsdf));
-          b->kind = m.kind == gvpm::MAT_ROUGHPLASTIC ? GVPM_BSDF_ROUGHPLASTIC : GVPM_BSDF_PLASTIC;
-          b->specular[0] = (float)m.spec.x; b->specular[1] = (float)m.spec.y; b->specular[2] = (float)m.spec.z;
-          b->exponent = (float)m.exponent;
-          b->specular_sampling_weight = (float)m.specWeight;
-          b->distribution = m.kind == gvpm::MAT_ROUGHPLASTIC ? m.distribution : 0;
-          b->sample_visible = 0;  // (the host walk samples all normals, synth_core.h)
-          b->eta[0] = (float)m.coatEta;
-          b->eta[1] = (float)m.fdr;
-          b->k[0] = m.kind == gvpm::MAT_PLASTIC ? 2.f : (entries == 2 ? (float)(c + 1) : 0.f);
-          b->k[1] = (float)m.nonlinear;
-          if (stride > 1 && m.rtrans) memcpy(b + 1, m.rtrans, GVPM_RTRANS_KNOTS * sizeof(float));
-        }
-        n += stride;
-      }
-      continue;
-    }
-    if (m.kind == gvpm::MAT_WARD_ANISO || m.kind == gvpm::MAT_ROUGHCONDUCTOR_ANISO) {
-      // a head with the fields of its isotropic sibling (exponent = alphaU), then the frame entry {tangent, alphaV, 0 x 12}
-      const int stride = 1 + GVPM_ANISO_ENTRIES;
-      if (out && (uint32_t)(m.bsdf + stride) <= cap) {
-        gvpm_bsdf *b = &out[m.bsdf];
-        memset(b, 0, stride * sizeof(gvpm_bsdf));
-        b->specular[0] = (float)m.spec.x; b->specular[1] = (float)m.spec.y; b->specular[2] = (float)m.spec.z;
-        b->exponent = (float)m.exponent;
-        if (m.kind == gvpm::MAT_WARD_ANISO) {
-          b->kind = GVPM_BSDF_WARD_ANISO;
-          b->specular_sampling_weight = (float)m.specWeight;
-          b->sample_visible = m.distribution;  // (the model variant)
-        } else {
-          b->kind = GVPM_BSDF_ROUGHCONDUCTOR_ANISO;
-          b->distribution = m.distribution;
-          b->sample_visible = 0;  // (the host walk samples all normals, synth_core.h)
-          b->eta[0] = (float)m.eta.x; b->eta[1] = (float)m.eta.y; b->eta[2] = (float)m.eta.z;
-          b->k[0] = (float)m.k.x; b->k[1] = (float)m.k.y; b->k[2] = (float)m.k.z;
-        }
-        // (a frame word is +0 or a normal float, gvpm_upload_bsdfs: a component that rounds below FLT_MIN becomes +0)
-        float frame[4] = {(float)m.tangent.x, (float)m.tangent.y, (float)m.tangent.z, (float)m.alphaV};
-        for (float &v : frame)
-          if (!(std::fabs(v) >= FLT_MIN)) v = 0.f;
-        memcpy(b + 1, frame, sizeof frame);
-      }
-      n += stride;
-      continue;
-    }
-    for (int c = 0; c < entries; ++c) {
-      if (out && (uint32_t)(m.bsdf + c) < cap) {
-        gvpm_bsdf &b = out[m.bsdf + c];
-        memset(&b, 0, sizeof(b));
-        b.specular[0] = (float)m.spec.x; b.specular[1] = (float)m.spec.y; b.specular[2] = (float)m.spec.z;
-        b.exponent = (float)m.exponent;
-        if (m.kind == gvpm::MAT_PHONG) {
-          b.kind = GVPM_BSDF_PHONG;
-          b.specular_sampling_weight = (float)m.specWeight;
-          b.distribution = entries == 2 ? c + 1 : 0;  // (sampled component + 1; 0: both components, include/gvpm_hip.h)
-        } else if (m.kind == gvpm::MAT_WARD) {
-          b.kind = GVPM_BSDF_WARD;
-          b.specular_sampling_weight = (float)m.specWeight;
-          b.sample_visible = m.distribution;  // (the model variant, include/gvpm_hip.h)
-        } else {
-          b.kind = GVPM_BSDF_ROUGHCONDUCTOR;
-          b.distribution = m.distribution;
-          b.sample_visible = 0;  // (the host walk samples all normals, synth_core.h)
-          b.eta[0] = (float)m.eta.x; b.eta[1] = (float)m.eta.y; b.eta[2] = (float)m.eta.z;
-          b.k[0] = (float)m.k.x; b.k[1] = (float)m.k.y; b.k[2] = (float)m.k.z;
-        }
-      }
-      ++n;
+    // a head per component met (Phong, rough plastic below roughness 0.05: one component alone, then the other), each followed
+    // by the raw entries of its kind
+    const int entries = gvpm::bsdfEntries(m.kind, m.exponent), kind = gvpm::matBsdfKind(m.kind);
+    const int stride = 1 + gvpm::bsdfTailEntries(kind);
+    for (int c = 0; c < entries; ++c, n += stride) {
+      if (!out || (uint32_t)(m.bsdf + (c + 1) * stride) > cap) continue;
+      gvpm_bsdf *b = &out[m.bsdf + c * stride];
+      memset(b, 0, stride * sizeof(gvpm_bsdf));
+      fillBsdf(m, kind, entries == 2 ? c + 1 : 0, b);
     }
   }
   return n;

@@ -10,6 +10,7 @@
 #include <limits>
 
 #include "../../include/gvpm_hip.h"
+#include "../csrc/bsdf_table.h"
 #include "philox.h"
 #include "vecmath.h"
 
@@ -52,12 +53,21 @@ GVPM_HD inline int bsdfEntries(int kind, double exponent) {
   if (kind == MAT_PLASTIC || kind == MAT_WARD_ANISO || kind == MAT_ROUGHCONDUCTOR_ANISO) return 1;
   return kind == MAT_PHONG ? (phongOneComponent(exponent) ? 2 : 1) : ((kind == MAT_ROUGHCONDUCTOR || kind == MAT_WARD) ? 1 : 0);
 }
-// table SLOTS of a material: a rough-plastic entry is a head followed by the raw entries of its slice, an anisotropic one a
-// head followed by its frame entry (include/gvpm_hip.h)
-GVPM_HD inline int bsdfSlots(int kind, double exponent) {
-  if (kind == MAT_WARD_ANISO || kind == MAT_ROUGHCONDUCTOR_ANISO) return 1 + GVPM_ANISO_ENTRIES;
-  return bsdfEntries(kind, exponent) * (kind == MAT_ROUGHPLASTIC ? 1 + GVPM_RTRANS_ENTRIES : 1);
+// the table kind of a glossy material's entries (0: the material has none)
+GVPM_HD inline int matBsdfKind(int kind) {
+  switch (kind) {
+    case MAT_PHONG: return GVPM_BSDF_PHONG;
+    case MAT_ROUGHCONDUCTOR: return GVPM_BSDF_ROUGHCONDUCTOR;
+    case MAT_WARD: return GVPM_BSDF_WARD;
+    case MAT_ROUGHPLASTIC: return GVPM_BSDF_ROUGHPLASTIC;
+    case MAT_PLASTIC: return GVPM_BSDF_PLASTIC;
+    case MAT_WARD_ANISO: return GVPM_BSDF_WARD_ANISO;
+    case MAT_ROUGHCONDUCTOR_ANISO: return GVPM_BSDF_ROUGHCONDUCTOR_ANISO;
+    default: return 0;
+  }
 }
+// table SLOTS of a material: every entry is a head followed by the raw entries of its kind (bsdf_table.h)
+GVPM_HD inline int bsdfSlots(int kind, double exponent) { return bsdfEntries(kind, exponent) * (1 + bsdfTailEntries(matBsdfKind(kind))); }
 
 struct SynthTri {
   V3 v0, e1, e2, n;  // n: geometric normal (front side)
@@ -70,7 +80,7 @@ struct SynthMat {
   double exponent;    // Phong exponent
   double specWeight;  // m_specularSamplingWeight = lum(spec) / (lum(diffuse) + lum(spec)), phong.cpp:93-97
   int bsdf;           // index in the table of gvpm_upload_bsdfs (-1: none); a Phong below roughness 0.05 has TWO entries:
-                      // bsdf = met through its specular component, bsdf + 1 = through its diffuse one (phongEntries)
+                      // bsdf = met through its specular component, bsdf + 1 = through its diffuse one (bsdfEntries)
   // rough conductor: spec = specular reflectance, exponent = alpha
   V3 eta = V3(0.0), k = V3(0.0);
   int distribution = 0;  // GVPM_MICROFACET_*
@@ -860,7 +870,7 @@ GVPM_HD inline int typeShift(const SceneView &sc, const LPath &p, size_t c) {
 // the head of the component it was sampled through
 GVPM_HD inline int plasticEntry(const SceneView &sc, const LVertex &par) {
 #if GVPM_SYNTH_GLOSSY
-  if (par.matKind == MAT_ROUGHPLASTIC) return sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 + GVPM_RTRANS_ENTRIES : 0);
+  if (par.matKind == MAT_ROUGHPLASTIC) return sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 + bsdfTailEntries(GVPM_BSDF_ROUGHPLASTIC) : 0);
   if (par.matKind == MAT_PLASTIC && par.compSel == 1) return sc.mats[par.mat].bsdf;
 #endif
   return -1;

@@ -8,7 +8,7 @@ import oracle_lib
 from gvpm_amd import abi
 from plastic_cases import relabelled, use_table  # noqa: F401  (the same record surgery)
 
-E = 1 + abi.GVPM_ANISO_ENTRIES  # table entries an anisotropic surface takes
+E = 1 + abi.bsdf_tail_entries(abi.GVPM_BSDF_WARD_ANISO)  # table entries an anisotropic surface takes
 # the walls of the cbox scenes that carry glossy materials (floor, back wall) and a tangent for each that is neither in the
 # wall nor along an axis: the device projects it
 WALL_N = np.array([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])

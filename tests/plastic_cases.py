@@ -12,7 +12,7 @@ import oracle_lib
 from gvpm_amd import abi
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rtrans_slices.npz")
-E = 1 + abi.GVPM_RTRANS_ENTRIES  # table entries a rough-plastic surface takes
+E = 1 + abi.bsdf_tail_entries(abi.GVPM_BSDF_ROUGHPLASTIC)  # table entries a rough-plastic surface takes
 
 
 def rtrans(dist, eta, alpha):

@@ -39,6 +39,9 @@ def test_bsdf_heads_covers_both_raw_entry_mechanisms():
     s, av = abi.frame_of(table, 0)
     assert list(s) == [1.0, 0.0, 0.0] and av == np.float32(0.3)
     assert (abi.GVPM_BSDF_WARD_ANISO, abi.GVPM_BSDF_ROUGHCONDUCTOR_ANISO, abi.GVPM_ANISO_ENTRIES) == (6, 8, 1)
+    tails = {abi.GVPM_BSDF_ROUGHPLASTIC: 7, abi.GVPM_BSDF_WARD_ANISO: 1, abi.GVPM_BSDF_ROUGHCONDUCTOR_ANISO: 1, abi.GVPM_BSDF_PHONG: 0,
+             abi.GVPM_BSDF_ROUGHCONDUCTOR: 0, abi.GVPM_BSDF_WARD: 0, abi.GVPM_BSDF_PLASTIC: 0}
+    assert {k: abi.bsdf_tail_entries(k) for k in tails} == tails
 
 
 @pytest.mark.parametrize("rot", ["", "_rot"])

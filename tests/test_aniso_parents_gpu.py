@@ -1,5 +1,5 @@
 """Anisotropic Ward and rough-conductor surface parents on the device (GVPM_BSDF_WARD_ANISO, GVPM_BSDF_ROUGHCONDUCTOR_ANISO;
-shift_device.h glossyParentEval): the gathers of every technique that reconnects against the numpy statement of
+parent_bsdf.h glossyParentEval): the gathers of every technique that reconnects against the numpy statement of
 tests/indep_aniso.py (the frozen fp64 oracle does not know the kinds: it fails these shifts), the equal-alpha limit in which the
 oracle does state them, tables the scenes do not have, the tangent's effect, the exact passes, the packed and linked uploads,
 and what gvpm_upload_bsdfs refuses.

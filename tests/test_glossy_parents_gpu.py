@@ -1,4 +1,4 @@
-"""Glossy surface parents on the device (GVPM_PARENT_SURFACE_BSDF + gvpm_upload_bsdfs; shift_device.h glossyParentEval):
+"""Glossy surface parents on the device (GVPM_PARENT_SURFACE_BSDF + gvpm_upload_bsdfs; parent_bsdf.h glossyParentEval):
 photons and beams behind S-cbox-phong's Phong floor and back wall are re-connected through the wall's whole BSDF
 (diffuseReconnection, shift_diffuse.cpp:25-47 with phong.cpp:121-186) -- for every technique that reconnects, against the
 fp64 oracle; without the table (or with an index beyond it) the same shifts fail, as they did before round 4."""

@@ -1,4 +1,4 @@
-"""Plastic surface parents on the device (GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC; shift_device.h glossyParentEval): the
+"""Plastic surface parents on the device (GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC; parent_bsdf.h glossyParentEval): the
 gathers of every technique that reconnects against the numpy statement of tests/indep_plastic.py (the frozen fp64 oracle
 has no plastic: it fails these shifts), the two limits in which the oracle does state them, the exact passes, the packed and
 linked uploads, and what gvpm_upload_bsdfs refuses."""
