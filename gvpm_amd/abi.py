@@ -164,6 +164,7 @@ GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC = 4, 5
 GVPM_RTRANS_KNOTS, GVPM_RTRANS_ENTRIES = 100, 7
 GVPM_BSDF_WARD_ANISO, GVPM_BSDF_ROUGHCONDUCTOR_ANISO = 6, 8   # (7 is not a kind)
 GVPM_ANISO_ENTRIES = 1
+GVPM_BSDF_ROUGHDIELECTRIC = 9   # (no raw entries behind the head; one entry per side of incidence)
 
 
 def bsdf_tail_entries(kind):
@@ -217,6 +218,16 @@ def aniso_entry(kind, specular, alpha_u, alpha_v, tangent, weight=0.0, variant=0
     raw[1, 0:3] = tangent
     raw[1, 3] = alpha_v
     return t
+
+
+def dielectric_entry(specular, transmittance, alpha, eta, distribution=0, sample_visible=0):
+    """one GVPM_BSDF_ROUGHDIELECTRIC entry (include/gvpm_hip.h): `eta` = the index behind the surface over the index on the side
+    the light arrived from -- a surface met from both sides has two entries, eta and 1 / eta"""
+    b = np.zeros(1, BSDF_DTYPE)
+    b["kind"], b["specular"], b["k"], b["exponent"] = GVPM_BSDF_ROUGHDIELECTRIC, specular, transmittance, alpha
+    b["distribution"], b["sample_visible"] = distribution, sample_visible
+    b["eta"][0, 0] = eta
+    return b
 
 
 def frame_of(table, head):

@@ -57,11 +57,20 @@ GVPM_TBL bool bsdfWardVariantValid(const gvpm_bsdf &b) {
   return b.sample_visible >= GVPM_WARD_WARD && b.sample_visible <= GVPM_WARD_BALANCED && b.distribution == 0;
 }
 
+// the rough dielectric's relative index as seen from wi's side: finite, within [0.2, 5] (either side of any real glass)
+GVPM_TBL bool bsdfDielectricEtaValid(float eta) { return eta >= 0.2f && eta <= 5.f; }
+GVPM_TBL bool bsdfChannelValid(float c) { return c >= 0.f && c <= 1.f; }
+// every word the rough dielectric leaves unused is +0
+GVPM_TBL bool bsdfDielectricZerosValid(const gvpm_bsdf &b) {
+  return (bsdfBits(b.eta[1]) | bsdfBits(b.eta[2]) | bsdfBits(b.specular_sampling_weight) | bsdfBits(b.reserved[0]) | bsdfBits(b.reserved[1])) == 0u;
+}
+
 // ---- a head's four rows ----
 //   row 0  {kind, specular.rgb}
 //   row 1  {exponent | alpha (alphaU), sampling weight, distribution | Phong component, sample_visible | Ward variant}
 //   row 2  {eta.rgb, k.r}         plastics: {eta, Fdr, -, component met}
 //   row 3  {k.g, k.b, 0, 0}       plastics: {nonlinear, ...}
+//   rough dielectric: row 2 {eta seen from wi's side, 0, 0, transmittance.r}, row 3 {transmittance.g, transmittance.b, 0, 0}
 // The integers travel as their bit patterns, the plastics' component and nonlinear flag as the floats they are in gvpm_bsdf.
 // The readers return a lane as it is stored and leave `!= 0` / `(int)` to the caller where the caller had them: moving such a
 // conversion into the reader changed the kernels' register allocation (NOTEBOOK.md, "one home for the BSDF table").
@@ -91,6 +100,9 @@ template <class R> GVPM_TBL float bsdfPlasticEta(const R &r2) { return r2.x; }
 template <class R> GVPM_TBL float bsdfPlasticFdr(const R &r2) { return r2.y; }
 template <class R> GVPM_TBL float bsdfPlasticComponent(const R &r2) { return r2.w; }  // 0.f both, 1.f glossy, 2.f diffuse
 template <class R> GVPM_TBL bool bsdfPlasticNonlinear(const R &r3) { return r3.x != 0.f; }
+// rows 2 and 3, the rough dielectric: the relative index seen from wi's side, channel C of the specular transmittance
+template <class R> GVPM_TBL float bsdfDielectricEta(const R &r2) { return r2.x; }
+template <int C, class R> GVPM_TBL float bsdfTransmittance(const R &r2, const R &r3) { return C == 0 ? r2.w : (C == 1 ? r3.x : r3.y); }
 // the frame entry behind an anisotropic head, as one row: {tangent.xyz, alphaV}
 template <class R> GVPM_TBL float bsdfFrameAlphaV(const R &fr) { return fr.w; }
 

@@ -114,7 +114,7 @@ __device__ void reconnectExact(const GatherArgs &a, const PhotonCold &ph, d3 off
     const double cosWo = dot(pn, dProj), cosWi = dot(pn, pwi);
     f3 f;
     float pdfF;
-    if (cosWi <= 0 || cosWo <= 0) return;
+    if (cosWi == 0 || cosWo <= 0) return;  // (cosWi < 0: a transmitted photon of a rough dielectric, glossyParentEval decides)
     // Phong: in fp64 (a lobe of exponent ~1000 underflows fp32 where the reference's double is still positive, and pdf == 0
     // is a decision); the rough conductor's values in fp32 -- the table's closed forms, parent_bsdf.h -- the DECISIONS
     // around them are taken here

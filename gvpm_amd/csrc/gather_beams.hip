@@ -366,7 +366,9 @@ __device__ __forceinline__ double shiftBeamDiffuse(const GatherArgs &a, const Ti
   double pdfValueSA;
   if (ptype == GVPM_PARENT_SURFACE || ptype == GVPM_PARENT_SURFACE_BSDF) {
     const double cosWo = dot(b.parentN, newPBDir), cosWi = dot(b.parentN, b.parentWi);
-    if (cosWi <= 0 || cosWo <= 0) return 1.0;  // eval = pdf = 0 (or the shading-normal reject): sRec.pdf == 0
+    // eval = pdf = 0 (or the shading-normal reject): sRec.pdf == 0; a glossy parent met from the other side (a transmitted
+    // photon of a rough dielectric) is glossyParentEval's to decide
+    if (cosWo <= 0 || (ptype == GVPM_PARENT_SURFACE_BSDF ? cosWi == 0 : cosWi <= 0)) return 1.0;
     thr = b.parentScat * (INV_PI * cosWo);
     pdfValueSA = INV_PI * cosWo;
     if (ptype == GVPM_PARENT_SURFACE_BSDF) {
@@ -945,7 +947,7 @@ __device__ __forceinline__ float reconnectBeamF(const GatherArgs &a, const BeamF
     const float cosWo = dot(b.parentN, nd), cosWi = dot(b.parentN, b.parentWi);
     // (the new beam's direction is good to ~1e-6: a cosine this close to zero is the exact pass's to sign)
     if (fabsf(cosWo) <= 1e-5f || fabsf(cosWi) <= 1e-5f) amb = true;
-    if (cosWi <= 0.f || cosWo <= 0.f) return 1.f;
+    if (cosWo <= 0.f || (ptype == GVPM_PARENT_SURFACE_BSDF ? cosWi == 0.f : cosWi <= 0.f)) return 1.f;
     thr = b.parentScat * (INV_PI_F * cosWo);
     pdfValueSA = INV_PI_F * cosWo;
     if (ptype == GVPM_PARENT_SURFACE_BSDF) {

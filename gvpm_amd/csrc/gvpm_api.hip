@@ -434,9 +434,20 @@ static int checkBsdf(gvpm_context *h, const gvpm_bsdf *table, uint32_t i, uint32
     if (rough)
       return checkBsdfTail(h, table, i, n, "rough plastic: the 7 entries of the transmittance slice are missing",
                            "rough plastic: slice values are finite, in [0, 1] and not subnormal; 12 zero words behind them");
+  } else if (b.kind == GVPM_BSDF_ROUGHDIELECTRIC) {
+    // (include/gvpm_hip.h: eta[0] = the index behind the surface over the index on wi's side, k = the specular transmittance)
+    if (!bsdfAlphaValid(b.exponent)) return fail(h, GVPM_ERR_INVALID_ARG, "rough dielectric: alpha >= 1e-4 (the reference clamps it)");
+    if (!bsdfDielectricEtaValid(b.eta[0])) return fail(h, GVPM_ERR_INVALID_ARG, "rough dielectric: eta[0] finite and in [0.2, 5]");
+    for (int c = 0; c < 3; ++c)
+      if (!bsdfChannelValid(b.specular[c]) || !bsdfChannelValid(b.k[c]))
+        return fail(h, GVPM_ERR_INVALID_ARG, "rough dielectric: reflectance and transmittance channels in [0, 1]");
+    if (!bsdfDielectricZerosValid(b))
+      return fail(h, GVPM_ERR_INVALID_ARG, "rough dielectric: eta[1], eta[2], the sampling weight and the reserved words are zero");
+    if (!bsdfMicrofacetValid(b)) return fail(h, GVPM_ERR_UNSUPPORTED, "rough dielectric: Beckmann or GGX");
   } else {
     return fail(h, GVPM_ERR_UNSUPPORTED,
-                "bsdf kind outside the device's closed set (Phong, rough conductor, Ward, the plastics, anisotropic Ward / rough conductor)");
+                "bsdf kind outside the device's closed set (Phong, rough conductor, Ward, the plastics, anisotropic Ward / rough conductor, "
+                "rough dielectric)");
   }
   return GVPM_OK;
 }

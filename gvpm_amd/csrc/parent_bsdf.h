@@ -111,15 +111,73 @@ __device__ __forceinline__ float roughTransmittance(const float *__restrict__ t,
   return fminf(fmaxf(r, 0.f), 1.f);
 }
 
+// fresnelDielectricExt for a cosine of either sign and any eta > 0 (src/libcore/util.cpp:659-689): a negative cosine meets the
+// inverse index; total internal reflection (cos^2(theta_T) <= 0) gives 1
+__device__ __forceinline__ float fresnelDielectricExt(float cI, float eta) {
+  if (eta == 1.f) return 0.f;
+  const float e = cI > 0.f ? eta : frcp(eta), c = fabsf(cI), ie = frcp(e);
+  if (1.f - (1.f - c * c) * (ie * ie) <= 0.f) return 1.f;
+  return fresnelDielectric(c, e);
+}
+
 // a head's specular reflectance (bsdf_table.h, row 0)
 __device__ __forceinline__ f3 bsdfSpecular3(const float4 b0) { return mk3(bsdfSpecular<0>(b0), bsdfSpecular<1>(b0), bsdfSpecular<2>(b0)); }
+
+// The rough dielectric (GVPM_BSDF_ROUGHDIELECTRIC; src/bsdfs/roughdielectric.cpp:270-422, include/gvpm_hip.h), the one kind that
+// transmits.  `n` is the record's normal, on the side the photon LEFT (cosWo > 0 is the caller's test): cosWi > 0 is reflection,
+// cosWi < 0 transmission.  Everything in wi's frame: nI = n sign(cosWi), ci = |cosWi|, co = +-cosWo, eta = the entry's index
+// behind the surface over the index on wi's side.  Returns {eval.rgb, pdf}; pdf < 0: |wi + wo eta|^2 < 1e-12, no half vector -- a
+// failed shift.  Inlined, and dispatched LAST in glossyParentEval: as a __noinline__ function handed everything by value it cost
+// seven to ten evaluation kernels scratch, inlined but dispatched first five (NOTEBOOK.md, "Rough-dielectric parents").
+__device__ __forceinline__ float4 roughDielectricEval(const float4 *__restrict__ e, f3 n, f3 wi, f3 wo, float cosWi, float cosWo) {
+  const float4 b0 = e[0], b1 = e[1], b2 = e[2], b3 = e[3];
+  const float sgn = cosWi > 0.f ? 1.f : -1.f, ci = fabsf(cosWi), co = cosWo * sgn;
+  const bool reflect = cosWi > 0.f;
+  const float eta = bsdfDielectricEta(b2), alpha = bsdfAlpha(b1);
+  const int ggx = bsdfDistribution(b1) == GVPM_MICROFACET_GGX, vis = bsdfSampleVisible(b1) != 0;
+  f3 H = reflect ? wi + wo : wi + wo * eta;
+  const float HH = dot(H, H);
+  if (HH < 1e-12f) return make_float4(0.f, 0.f, 0.f, -1.f);
+  H = H * frsq(HH);
+  float cH = dot(H, n) * sgn;  // (the half vector in nI's hemisphere, :300-302)
+  if (cH < 0.f) {
+    H = -H;
+    cH = -cH;
+  }
+  const float wiH = dot(wi, H), woH = dot(wo, H);
+  // D of the surface's alpha, and the D the half vector was sampled with: the same for visible normals, else at the alpha Walter's
+  // trick scaled (:406-414) with its own `D' cos_H < 1e-20` cut.  D == 0 gives eval = 0 (:315-316) -- and pdf = 0 only if D' is
+  // zero too: RoughDielectric::pdf does not look at D, so a half vector in the band between the two cuts is a shift that
+  // SUCCEEDS with zero flux (the products below are 0 x finite)
+  const float D = microfacetD(ggx, alpha, cH);
+  const float Ds = vis ? D : microfacetD(ggx, alpha * (1.2f - 0.2f * fsqrt(ci)), cH);
+  if (D == 0.f && Ds == 0.f) return make_float4(0.f, 0.f, 0.f, 0.f);
+  const float F = fresnelDielectricExt(wiH, eta);
+  const float G1i = microfacetG1(ggx, alpha, ci, wiH), G1o = microfacetG1(ggx, alpha, co, woH);
+  f3 f;
+  float dwh;
+  if (reflect) {
+    f = bsdfSpecular3(b0) * fdiv(F * D * G1i * G1o, 4.f * ci);
+    dwh = frcp(4.f * woH);
+  } else {
+    const float sD = wiH + eta * woH, e2 = fdiv(eta * eta, sD * sD);
+    // (EImportance: no solid-angle compression factor, :339-343)
+    f = mk3(bsdfTransmittance<0>(b2, b3), bsdfTransmittance<1>(b2, b3), bsdfTransmittance<2>(b2, b3)) *
+        fabsf(fdiv((1.f - F) * D * G1i * G1o * e2 * wiH * woH, ci));
+    dwh = e2 * woH;
+  }
+  // the sampling density of the half vector: visible normals, or all normals
+  const float prob = vis ? fdiv(D * G1i * fabsf(wiH), ci) : Ds * cH;
+  return make_float4(f.x, f.y, f.z, fabsf(prob * dwh) * (reflect ? F : 1.f - F));
+}
 
 // A glossy surface parent (GVPM_PARENT_SURFACE_BSDF): BSDF::eval and BSDF::pdf * pdfComponent of the table entry the
 // record names, towards the new direction `wo` (shift_diffuse.cpp:25-41 with bRec.component = -1).  Phong, src/bsdfs/
 // phong.cpp:121-186: eval = (ks (e + 2) / 2pi alpha^e + kd / pi) cos_o, pdf = w alpha^e (e + 1) / 2pi + (1 - w) cos_o / pi,
 // alpha = wo . reflect(wi).  Rough conductor, src/bsdfs/roughconductor.cpp:257-319: eval = F D G / (4 cos_i), pdf = D G1(wi)
-// / (4 cos_i) or D cos_H / (4 |wo . H|) (include/gvpm_hip.h).  cosWi, cosWo > 0 is the caller's test.  False: no such
-// entry (a failed shift).
+// / (4 cos_i) or D cos_H / (4 |wo . H|) (include/gvpm_hip.h).  cosWo > 0 and cosWi != 0 is the caller's test; cosWi < 0 (the
+// light arrived on the other side: a transmitted photon) is the rough dielectric's alone, every other kind fails the shift.
+// False: no such entry (a failed shift).
 // state (optional out, round 5): bit 0 -- the pdf is POSITIVE in double precision although it underflowed here (the
 // specular component of a Phong wall alone, exponent ~1000: alpha^e leaves fp32 below alpha ~ 0.94 and fp64 only below ~0.6;
 // with pdf == 0 the reference fails the shift, with a positive one -- however small -- it succeeds, with weight 1 and a
@@ -133,7 +191,8 @@ __device__ __forceinline__ bool glossyParentEval(const GatherArgs &a, float inde
   if (state) *state = 0u;
   if (!(index >= 0.f) || bi >= a.nbsdfs) return false;
   const float4 b0 = a.bsdfs[4 * bi], b1 = a.bsdfs[4 * bi + 1];
-  const int kind = bsdfKind(b0);
+  // (a record met from behind, cosWi <= 0, reads as no kind unless its entry is the rough dielectric's: a failed shift)
+  const int kind = (cosWi > 0.f || bsdfKind(b0) == GVPM_BSDF_ROUGHDIELECTRIC) ? bsdfKind(b0) : 0;
   if (kind == GVPM_BSDF_PHONG) {
     // (the sampling weight is read as the lane it is: through bsdfSamplingWeight the compiler swaps the operands of a mask
     // `and` in the G-VPM kernels, and this change leaves every instruction where it was -- NOTEBOOK.md)
@@ -258,6 +317,13 @@ __device__ __forceinline__ bool glossyParentEval(const GatherArgs &a, float inde
     pdf = pS * pdfM + (1.f - pS) * (INV_PI_F * cosWo * dOn);
     return true;
   }
+  if (kind == GVPM_BSDF_ROUGHDIELECTRIC) {
+    const float4 r = roughDielectricEval(a.bsdfs + 4 * bi, n, wi, wo, cosWi, cosWo);
+    if (r.w < 0.f) return false;
+    f = mk3(r.x, r.y, r.z);
+    pdf = r.w;
+    return true;
+  }
   return false;
 }
 
@@ -269,7 +335,7 @@ __device__ __forceinline__ bool phongEvalD(const GatherArgs &a, float index, d3 
   const uint32_t bi = (uint32_t)index;
   if (!(index >= 0.f) || bi >= a.nbsdfs) return false;
   const float4 b0 = a.bsdfs[4 * bi], b1 = a.bsdfs[4 * bi + 1];
-  if (bsdfKind(b0) != GVPM_BSDF_PHONG) return false;
+  if (bsdfKind(b0) != GVPM_BSDF_PHONG || !(cosWi > 0)) return false;  // (cosWi <= 0: glossyParentEval fails the shift)
   const double INV_PI = 0.31830988618379067154, INV_TWOPI = 0.15915494309189533577;
   const double e = bsdfExponent(b1), w = bsdfSamplingWeight(b1);
   const int comp = bsdfPhongComponent(b1);  // 0 both, 1 specular only, 2 diffuse only (gvpm_hip.h, gvpm_bsdf)

@@ -159,7 +159,9 @@ __device__ __forceinline__ float shiftDiffuse(const GatherArgs &a, const PhotonC
   good = good && (isMedium || cosWo * dot(ph.parentN, -ph.wi) >= 0.f);
   // eval / pdf of the parent towards the offset position (diffuse.cpp:110-127, phase eval, area.cpp:132-150)
   const float cosWi = dot(ph.parentN, ph.parentWi);
-  good = good && (!isSurface || (cosWi > 0.f && cosWo > 0.f));  // eval/pdf = 0 or the shading-normal reject
+  // eval/pdf = 0 or the shading-normal reject; a glossy parent may have been met from the other side (a transmitted photon of a
+  // rough dielectric: glossyParentEval decides)
+  good = good && (!isSurface || (cosWo > 0.f && (isGlossy ? cosWi != 0.f : cosWi > 0.f)));
   const float lam = INV_PI_F * fmaxf(cosWo, 0.f);
   const float pMed = phaseEval(ph.parentG, ph.parentWi, dProj);
   float pdfValue = isMedium ? pMed : lam;

@@ -52,6 +52,8 @@ def lib():
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
         L.gvpm_synth_sample_aniso.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
+        L.gvpm_synth_sample_dielectric.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gvpm_synth_sensor.argtypes = [C.c_void_p, C.POINTER(abi.Sensor)]
         L.gvpm_synth_jitter.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
         _LIB = L
@@ -144,6 +146,19 @@ class SynthScene:
         if rc < 0:
             raise ValueError(f"sample_aniso({mat}): not an anisotropic material")
         return (wo, weight, pdf.value) if rc == 1 else None
+
+    def sample_dielectric(self, mat, n, wi, u1, u2, u3):
+        """one bounce off or through rough-dielectric material `mat` as the light-path walk takes it (`n`: the surface's front normal,
+        wi on either side of it; u3: the number of the reflect / transmit choice): (wo, weight, pdf, sampled type 0x8 | 0x10) or
+        None when the sample is lost"""
+        n, wi = np.ascontiguousarray(n, np.float64), np.ascontiguousarray(wi, np.float64)
+        wo, weight = np.zeros(3), np.zeros(3)
+        pdf, comp = C.c_double(0), C.c_int(0)
+        rc = lib().gvpm_synth_sample_dielectric(self._h, mat, n.ctypes.data, wi.ctypes.data, u1, u2, u3, wo.ctypes.data,
+                                                weight.ctypes.data, C.addressof(pdf), C.addressof(comp))
+        if rc < 0:
+            raise ValueError(f"sample_dielectric({mat}): not a rough-dielectric material")
+        return (wo, weight, pdf.value, comp.value) if rc == 1 else None
 
     def sensor(self):
         """the scene's pinhole sensor (gvpm_sensor) the compact beam sets are decoded with"""

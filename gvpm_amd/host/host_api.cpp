@@ -193,6 +193,21 @@ int gvpm_synth_sample_aniso(const gvpm_synth *s, int mat, const double *n, const
   return 1;
 }
 
+int gvpm_synth_sample_dielectric(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double u3,
+                                 double *wo, double *weight, double *pdf, int *component) {
+  using namespace gvpm;
+  if (!s || !n || !wi || !wo || !weight || !pdf || !component || mat < 0 || mat >= (int)s->scene.mats.size()) return GVPM_ERR_INVALID_ARG;
+  const SynthMat &pm = s->scene.mats[mat];
+  if (pm.kind != MAT_ROUGHDIELECTRIC) return GVPM_ERR_INVALID_ARG;
+  V3 o, w;
+  uint32_t comp = 0;
+  if (!sampleDielectric(pm, V3(n[0], n[1], n[2]), V3(wi[0], wi[1], wi[2]), u1, u2, u3, o, w, *pdf, comp)) return 0;
+  wo[0] = o.x; wo[1] = o.y; wo[2] = o.z;
+  weight[0] = w.x; weight[1] = w.y; weight[2] = w.z;
+  *component = (int)comp;
+  return 1;
+}
+
 // One head of material `m` (`component`: the one it is met through + 1 where an entry per component exists, else 0) and the raw
 // entries behind it (bsdf_table.h); `b` points at 1 + bsdfTailEntries(kind) zeroed entries.
 static void fillBsdf(const gvpm::SynthMat &m, int kind, int component, gvpm_bsdf *b) {
@@ -214,6 +229,12 @@ static void fillBsdf(const gvpm::SynthMat &m, int kind, int component, gvpm_bsdf
     b->eta[1] = (float)m.fdr;
     b->k[0] = kind == GVPM_BSDF_PLASTIC ? 2.f : (float)component;
     b->k[1] = (float)m.nonlinear;
+  }
+  if (kind == GVPM_BSDF_ROUGHDIELECTRIC) {
+    // one entry per side of incidence (component 1: met from the front, 2: from the back): the index behind over the index before
+    b->specular_sampling_weight = 0.f;
+    b->eta[0] = (float)(component == 2 ? 1.0 / m.coatEta : m.coatEta);
+    b->k[0] = (float)m.k.x; b->k[1] = (float)m.k.y; b->k[2] = (float)m.k.z;
   }
   if (kind == GVPM_BSDF_ROUGHPLASTIC) {
     if (m.rtrans) memcpy(b + 1, m.rtrans, GVPM_RTRANS_KNOTS * sizeof(float));

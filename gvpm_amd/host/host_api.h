@@ -50,6 +50,12 @@ int gvpm_synth_sample_plastic(const gvpm_synth *s, int mat, const double *n, con
  * GVPM_ERR_INVALID_ARG for another kind of material. */
 int gvpm_synth_sample_aniso(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
                             double *weight, double *pdf);
+/* A TEST HOOK like gvpm_synth_sample_plastic, for the rough-dielectric material (scenes cbox_roughglass*; synth_core.h
+ * sampleDielectric): one bounce off or through the surface whose FRONT normal is n, wi on either side of it; u3 = the random
+ * number of the reflect / transmit choice.  Returns 1 and wo, weight, pdf (solid angle), *component = the sampled type
+ * (0x8 EGlossyReflection, 0x10 EGlossyTransmission); 0 when the sample is lost; GVPM_ERR_INVALID_ARG for another kind of material. */
+int gvpm_synth_sample_dielectric(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double u3,
+                                 double *wo, double *weight, double *pdf, int *component);
 /* the BSDF table of the scene's glossy walls (a rough-plastic head is followed by the raw entries of its slice, an anisotropic head by its
  * frame entry), in the order the photons' parent_g name them (gvpm_upload_bsdfs);
  * returns the number of entries (at most cap are written) */

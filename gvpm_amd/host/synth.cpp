@@ -318,6 +318,29 @@ bool makeScene(const std::string &fullName, int width, int height, uint32_t seed
     if (rot) addCornellBlocks(s, 0, mBack);
     setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);
     setMedium(s, 0.5, 0.5, 0.0);
+  } else if (name == "cbox_roughglass" || name == "cbox_roughglass_ggx") {
+    // S-cbox with Lambertian walls and a ROUGH-GLASS pane across the whole room under the light (row f4; src/bsdfs/
+    // roughdielectric.cpp -- a material of the bathroom scene BASELINE configs[3] is named after): eta 1.5, Beckmann alpha 0.25, its
+    // front (the side eta belongs to) up.  Everything below the pane is lit through it: photons behind it were transmitted,
+    // photons above it reflected, and light that comes back from the room meets it from inside.  Reflectance and transmittance
+    // are tinted differently, so that a swapped pair shows.  `_rot`: the pane is tilted in the room as well, its plane in
+    // general position there -- a parent's fp32 position falls either side of it.  `cbox_roughglass_ggx`: the same pane with
+    // the GGX distribution.
+    SynthMat m{MAT_ROUGHDIELECTRIC, V3(0.0), V3(1.0, 0.95, 0.9), 0.25, 0.0, 0};
+    m.coatEta = 1.5;
+    m.k = V3(0.9, 0.95, 1.0);
+    m.distribution = name == "cbox_roughglass_ggx" ? GVPM_MICROFACET_GGX : GVPM_MICROFACET_BECKMANN;
+    m.bsdf = 0;
+    for (const auto &q : s.mats) m.bsdf += bsdfSlots(q.kind, q.exponent);
+    s.mats.push_back(m);
+    const int mPane = (int)s.mats.size() - 1;
+    addBoxRoom(s, 0, 0, 0, 1, 2, 3);
+    if (rot) addCornellBlocks(s, 0, 0);
+    const double tx = rot ? 0.06 : 0.0, tz = rot ? -0.04 : 0.0;
+    auto P = [&](double x, double z) { return V3(x, 0.55 + tx * x + tz * z, z); };
+    s.addQuad(P(-1, -1), P(-1, 1), P(1, 1), P(1, -1), mPane);  // n = up
+    setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);
+    setMedium(s, 0.5, 0.5, 0.0);
   } else if (name == "cbox") {
     addBoxRoom(s, 0, 0, 0, 1, 2, 3);
     if (rot) addCornellBlocks(s, 0, 0);

@@ -33,6 +33,11 @@ namespace gvpm {
 // MAT_WARD_ANISO, MAT_ROUGHCONDUCTOR_ANISO: the same two plugins with alphaU (`exponent`) != alphaV (`alphaV`) on a PLANAR
 // surface whose world-space tangent is `tangent` (the shading frame's s, the direction alphaU belongs to); the table's
 // GVPM_BSDF_WARD_ANISO / GVPM_BSDF_ROUGHCONDUCTOR_ANISO head + frame entry (include/gvpm_hip.h)
+// MAT_ROUGHDIELECTRIC: src/bsdfs/roughdielectric.cpp, isotropic Beckmann / GGX, sampled without visible normals: rough glass, met
+// from BOTH sides and the one material that TRANSMITS.  `exponent` = alpha, `coatEta` = m_eta (the index below the triangle's front
+// over the index above it), `spec` = the specular reflectance, `k` = the specular transmittance.  Two table entries: bsdf = met
+// from the front, bsdf + 1 = met from the back (include/gvpm_hip.h: one entry per side of incidence).  The single global medium
+// lies on both sides.
 // The glossy kinds are sampled by the HOST generators only: the device generator's closed set is Lambertian / index-matched /
 // mirror (gvpm_devgen_create refuses the others), and their fp64 pow / atan / log chains cost the device walk a third of its
 // time in registers alone when they were merely compiled in.
@@ -42,7 +47,7 @@ namespace gvpm {
 #define GVPM_SYNTH_GLOSSY 1
 #endif
 enum MatKind { MAT_LAMBERT = 0, MAT_NULL = 1, MAT_MIRROR = 2, MAT_PHONG = 3, MAT_ROUGHCONDUCTOR = 4, MAT_WARD = 5, MAT_ROUGHPLASTIC = 6,
-               MAT_PLASTIC = 7, MAT_WARD_ANISO = 8, MAT_ROUGHCONDUCTOR_ANISO = 9 };
+               MAT_PLASTIC = 7, MAT_WARD_ANISO = 8, MAT_ROUGHCONDUCTOR_ANISO = 9, MAT_ROUGHDIELECTRIC = 10 };
 // table entries of a glossy material: PathVertex::sampleNext picks ONE component of a Phong surface below roughness 0.05
 // (vertex.cpp:160-165, Phong::getRoughness = sqrt(2 / (2 + exponent)), phong.cpp:293-300): an entry per component then
 GVPM_HD inline bool phongOneComponent(double exponent) { return sqrt(2.0 / (2.0 + exponent)) < 0.05; }
@@ -50,6 +55,7 @@ GVPM_HD inline bool phongOneComponent(double exponent) { return sqrt(2.0 / (2.0 
 // its diffuse component alone, the Dirac one is a specular vertex)
 GVPM_HD inline int bsdfEntries(int kind, double exponent) {
   if (kind == MAT_ROUGHPLASTIC) return exponent < 0.05 ? 2 : 1;
+  if (kind == MAT_ROUGHDIELECTRIC) return 2;  // (one per side of incidence, at every roughness: sampleComponent returns -1)
   if (kind == MAT_PLASTIC || kind == MAT_WARD_ANISO || kind == MAT_ROUGHCONDUCTOR_ANISO) return 1;
   return kind == MAT_PHONG ? (phongOneComponent(exponent) ? 2 : 1) : ((kind == MAT_ROUGHCONDUCTOR || kind == MAT_WARD) ? 1 : 0);
 }
@@ -63,6 +69,7 @@ GVPM_HD inline int matBsdfKind(int kind) {
     case MAT_PLASTIC: return GVPM_BSDF_PLASTIC;
     case MAT_WARD_ANISO: return GVPM_BSDF_WARD_ANISO;
     case MAT_ROUGHCONDUCTOR_ANISO: return GVPM_BSDF_ROUGHCONDUCTOR_ANISO;
+    case MAT_ROUGHDIELECTRIC: return GVPM_BSDF_ROUGHDIELECTRIC;
     default: return 0;
   }
 }
@@ -404,6 +411,79 @@ inline bool sampleAniso(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 
   return maxc(weight) > 0 && pdf > 0;
 }
 
+// fresnelDielectricExt with the transmitted cosine (util.cpp:659-689): a cosine of either sign against a relative index eta
+GVPM_HD inline double dielectricFresnelExt(double cI_, double &cT_, double eta) {
+  if (eta == 1.0) {
+    cT_ = -cI_;
+    return 0.0;
+  }
+  const double scale = cI_ > 0 ? 1 / eta : eta, cT2 = 1 - (1 - cI_ * cI_) * (scale * scale);
+  if (cT2 <= 0.0) {
+    cT_ = 0.0;
+    return 1.0;
+  }
+  const double cI = std::fabs(cI_), cT = std::sqrt(cT2);
+  const double Rs = (cI - eta * cT) / (cI + eta * cT), Rp = (eta * cI - cT) / (eta * cI + cT);
+  cT_ = cI_ > 0 ? -cT : cT;
+  return 0.5 * (Rs * Rs + Rp * Rp);
+}
+
+// One bounce off or through a rough dielectric: RoughDielectric::sample with bRec.component = -1 and without visible normals
+// (roughdielectric.cpp:513-617), in wi's frame -- nI = n sign(n . wi), eta = m_eta where wi lies on the triangle's front, else
+// m_invEta (what the reference's frame with its signed cosines amounts to).  (a, b) = (sample.x, sample.y); c = the random
+// number of the reflect / transmit choice (bRec.sampler->next1D(), :554-560).  The half vector comes from
+// MicrofacetDistribution::sampleAll at the alpha Walter's trick scaled, 1.2 - 0.2 sqrt(|cos_i|) (:537-544); weight =
+// |D G wi.m / (pdf_m cos_i)| times the reflectance or the transmittance (EImportance: no compression factor), D and G at the
+// surface's own alpha; pdf = D'(m) cos_m (F | 1 - F) |dwh_dwo| (include/gvpm_hip.h).  False: the sample is lost.
+inline bool sampleDielectric(const SynthMat &pm, V3 n, V3 wi, double a, double b, double c, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
+  const double cosN = dot(n, wi);
+  if (cosN == 0) return false;
+  const V3 nI = cosN > 0 ? n : -n;
+  const double ci = std::fabs(cosN), eta = cosN > 0 ? pm.coatEta : 1.0 / pm.coatEta;
+  const int ggx = pm.distribution == GVPM_MICROFACET_GGX;
+  const double alpha = pm.exponent, alphaS = alpha * (1.2 - 0.2 * std::sqrt(ci)), alphaSqr = alphaS * alphaS;
+  double tanThetaMSqr, pdfM, cosThetaM;
+  if (ggx) {
+    tanThetaMSqr = alphaSqr * a / (1.0 - a);
+    cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
+    const double temp = 1 + tanThetaMSqr / alphaSqr;
+    pdfM = kInvPi / (alphaSqr * cosThetaM * cosThetaM * cosThetaM * temp * temp);
+  } else {
+    tanThetaMSqr = alphaSqr * -std::log(1.0 - a);
+    cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
+    pdfM = (1.0 - a) / (kPi * alphaSqr * cosThetaM * cosThetaM * cosThetaM);
+  }
+  if (!(pdfM >= 1e-20)) return false;
+  const double sinThetaM = std::sqrt(std::fmax(0.0, 1 - cosThetaM * cosThetaM)), phi = 2.0 * kPi * b;
+  const V3 m = toWorld(nI, V3(sinThetaM * std::cos(phi), sinThetaM * std::sin(phi), cosThetaM));
+  const double wiM = dot(wi, m);
+  double cosThetaT;
+  const double F = dielectricFresnelExt(wiM, cosThetaT, eta);
+  const bool reflect = !(c > F);
+  double dwh;
+  if (reflect) {
+    wo = m * (2.0 * wiM) - wi;
+    comp = 0x00008u;  // EGlossyReflection
+    if (dot(nI, wo) <= 0) return false;  // side check
+    weight = pm.spec;
+    dwh = 1.0 / (4.0 * dot(wo, m));
+  } else {
+    if (cosThetaT == 0) return false;
+    const double e = cosThetaT < 0 ? 1.0 / eta : eta;  // refract(wi, m, eta, cosThetaT), util.cpp:775-780
+    wo = m * (wiM * e + cosThetaT) - wi * e;
+    comp = 0x00010u;  // EGlossyTransmission
+    if (dot(nI, wo) >= 0) return false;  // side check
+    weight = pm.k;
+    const double be = cosThetaT < 0 ? eta : 1.0 / eta, sD = wiM + be * dot(wo, m);  // bRec.eta
+    dwh = be * be * dot(wo, m) / (sD * sD);
+  }
+  const double co = dot(nI, wo), woM = dot(wo, m);
+  const double D = conductorD(ggx, alpha, cosThetaM), G = conductorG1(ggx, alpha, ci, wiM) * conductorG1(ggx, alpha, co, woM);
+  weight = weight * std::fabs(D * G * wiM / (pdfM * ci));
+  pdf = conductorD(ggx, alphaS, cosThetaM) * cosThetaM * (reflect ? F : 1 - F) * std::fabs(dwh);
+  return maxc(weight) > 0 && pdf > 0;
+}
+
 // One bounce off a plastic surface as PathVertex::sampleNext does it (vertex.cpp:160-173): component selection, BSDF::sample
 // with bRec.component, then weight /= pdfComponent, pdf *= pdfComponent.  (a, b): the vertex's two random numbers (sample.x,
 // sample.y).  False: the sample is lost (the walk ends).  solidAngle = false: a Dirac bounce, pdf in the discrete measure.
@@ -579,7 +659,7 @@ template <class PATH> GVPM_HD inline bool walkStep(const SceneView &sc, Philox &
         // index-matched medium boundary: passes straight through and leaves the fog
         return false;
       }
-      if (dot(cur.n, wi) <= 0) return false;  // one-sided BSDFs
+      if (dot(cur.n, wi) <= 0 && cur.matKind != MAT_ROUGHDIELECTRIC) return false;  // one-sided BSDFs
       if (cur.matKind == MAT_MIRROR) {
         // Dirac reflection: weight = reflectance, pdf = 1 in the discrete measure (not converted to area below)
         wo = cur.n * (2.0 * dot(cur.n, wi)) - wi;
@@ -728,6 +808,11 @@ template <class PATH> GVPM_HD inline bool walkStep(const SceneView &sc, Philox &
         if (!sampleAniso(sc.mats[cur.mat], cur.n, wi, a, b, wo, cur.weight, cur.pdf, cur.comp)) return false;
       } else if (cur.matKind == MAT_ROUGHPLASTIC || cur.matKind == MAT_PLASTIC) {
         if (!samplePlastic(sc.mats[cur.mat], cur.n, wi, a, b, wo, cur.weight, cur.pdf, cur.comp, cur.compSel, solidAngle)) return false;
+      } else if (cur.matKind == MAT_ROUGHDIELECTRIC) {
+        // (one more number of the vertex's stream for the reflect / transmit choice, drawn at vertices of this material only:
+        // every other scene keeps its streams)
+        const double c = rng.next1D();
+        if (!sampleDielectric(sc.mats[cur.mat], cur.n, wi, a, b, c, wo, cur.weight, cur.pdf, cur.comp)) return false;
 #endif
       } else {
         V3 local = cosineHemisphere(a, b);
@@ -849,6 +934,7 @@ GVPM_HD inline bool vertexIsDiffuse(const SceneView &sc, const LVertex &v) {
 #if GVPM_SYNTH_GLOSSY
       if (v.matKind == MAT_ROUGHPLASTIC || (v.matKind == MAT_PLASTIC && v.compSel == 1)) return true;
       if (v.matKind == MAT_WARD_ANISO || v.matKind == MAT_ROUGHCONDUCTOR_ANISO) return true;  // (alphas far above bounceRoughness)
+      if (v.matKind == MAT_ROUGHDIELECTRIC) return true;  // (RoughDielectric::getRoughness = alpha, far above it too)
 #endif
       return v.matKind == MAT_LAMBERT || v.matKind == MAT_PHONG || v.matKind == MAT_ROUGHCONDUCTOR || v.matKind == MAT_WARD;
     case VT_MEDIUM: return !(sc.medium.g > 0.5);
@@ -874,6 +960,20 @@ GVPM_HD inline int plasticEntry(const SceneView &sc, const LVertex &par) {
   if (par.matKind == MAT_PLASTIC && par.compSel == 1) return sc.mats[par.mat].bsdf;
 #endif
   return -1;
+}
+
+// A vertex on a rough dielectric as a parent (include/gvpm_hip.h): the record's normal points to the side the path LEFT on --
+// towards `next`, the vertex behind it -- and it names the entry of the side the light ARRIVED on, from `prev`.  False: not
+// such a vertex.
+template <class REC> GVPM_HD inline bool dielectricParent(const SceneView &sc, const LVertex &par, V3 prev, V3 next, REC &r) {
+#if GVPM_SYNTH_GLOSSY
+  if (par.matKind == MAT_ROUGHDIELECTRIC) {
+    if (dot(par.n, next - par.pos) < 0) r.parentN = -par.n;
+    r.parentG = (float)(sc.mats[par.mat].bsdf + (dot(par.n, prev - par.pos) < 0 ? 1 : 0));
+    return true;
+  }
+#endif
+  return false;
 }
 
 struct PhotonRec {
@@ -917,6 +1017,7 @@ template <class PATH> GVPM_HD inline void fillParent(const SceneView &sc, const 
       ptype = GVPM_PARENT_SURFACE_BSDF;
       r.parentG = (float)plasticEntry(sc, par);
     }
+    if (dielectricParent(sc, par, path[ip - 1].pos, path[ip + 1].pos, r)) ptype = GVPM_PARENT_SURFACE_BSDF;
 #endif
   } else if (par.type == VT_MEDIUM) {
     ptype = GVPM_PARENT_MEDIUM;
@@ -1006,6 +1107,10 @@ template <class RL> GVPM_HD inline void flattenPath(const SceneView &sc, const L
         comp = par.comp;
       } else if (par.matKind == MAT_PLASTIC) {
         comp = 0x00008u;  // met through its Dirac component: as a mirror
+      }
+      if (dielectricParent(sc, par, path[i - 2].pos, path[i].pos, r)) {
+        ptype = GVPM_PARENT_SURFACE_BSDF;
+        comp = par.comp;  // EGlossyReflection or EGlossyTransmission
       }
 #endif
     } else if (par.type == VT_MEDIUM) {
@@ -1117,6 +1222,10 @@ template <class RL, bool BEAMS> struct StreamPath {
             comp = par.comp;
           } else if (par.matKind == MAT_PLASTIC) {
             comp = 0x00008u;
+          }
+          if (dielectricParent(sc, par, path[i - 2].pos, path[i].pos, r)) {
+            ptype = GVPM_PARENT_SURFACE_BSDF;
+            comp = par.comp;
           }
 #endif
         } else if (par.type == VT_MEDIUM) {

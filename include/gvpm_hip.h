@@ -46,7 +46,7 @@ extern "C" {
 
 #define GVPM_ABI_VERSION 3  /* 2: gvpm_bsdf grew to 64 bytes (rough conductor), round 4; 3: gvpm_devgen_scene carries the
                               sensor's rotation (cam_to_world), round 5.  Table kinds and entry points are ADDITIONS and
-                              do not bump it (GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC, the two _ANISO kinds: same 64-byte gvpm_bsdf) */
+                              do not bump it (GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC, the two _ANISO kinds, GVPM_BSDF_ROUGHDIELECTRIC: same 64-byte gvpm_bsdf) */
 
 /* ---- status codes --------------------------------------------------------*/
 typedef enum gvpm_status {
@@ -262,9 +262,45 @@ typedef struct gvpm_medium {
  *     whose distribution is not Beckmann or GGX (the Phong / Ashikhmin-Shirley one).  alphaU == alphaV is legal: the isotropic
  *     kind, whatever the tangent.  Photons name HEAD indices only.  GVPM_ANISO_ENTRIES = the raw entries behind such a head.
  *     (7 is not a kind.)
+ *   GVPM_BSDF_ROUGHDIELECTRIC  src/bsdfs/roughdielectric.cpp:270-422 with an isotropic, untextured Beckmann or GGX distribution: the
+ *     one kind that TRANSMITS.  RoughDielectric::sampleComponent returns -1 and pdfComponent 1 at every roughness (:647-657), so
+ *     there is no entry per component: reflection and transmission are both in play at every vertex.  Two conventions:
+ *     (1) THE RECORD'S NORMAL POINTS TO THE SIDE THE PHOTON LEFT: for a record that names an entry of this kind, parent_n is the
+ *     surface normal oriented so that dot(parent_n, pos - parent_pos) > 0 (a host that has the shading normal flips it where the
+ *     photon was transmitted).  Admissible offset directions then satisfy cos(theta_o) = parent_n . wo > 0 as for every other
+ *     surface parent (the reference's sign test, shift_volume_photon.cpp:404-412, keeps the shifted direction on the base's
+ *     side), and the photon's class is read off the record: cos(theta_i) = parent_n . parent_wi > 0 is REFLECTION, < 0 is
+ *     TRANSMISSION, == 0 gives eval = 0 (:271), a failed shift.
+ *     (2) ONE ENTRY PER SIDE OF INCIDENCE: eval and pdf depend on the surface's orientation only through the index wi lies in,
+ *     so eta[0] = the index BEHIND the surface divided by the index ON wi's SIDE -- m_eta where the light arrived on the outside,
+ *     m_invEta where it arrived inside.  A surface that can be met both ways has two entries; the photon names the entry of the
+ *     side it was met from.
+ *     With nI = parent_n sign(cos(theta_i)) (the normal on wi's side), ci = |cos(theta_i)|, eta = eta[0] and cosines taken
+ *     against nI (cos_o = +-parent_n . wo):
+ *       reflection (:279-286, 324-329, 365-375):  H = normalize(wi + wo),
+ *         eval = specular F D G / (4 ci),  dwh_dwo = 1 / (4 wo . H)
+ *       transmission (:287-298, 330-347, 376-391):  H = normalize(wi + wo eta), flipped into nI's hemisphere,
+ *         sD = wi . H + eta wo . H,
+ *         eval = k |(1 - F) D G eta^2 (wi . H)(wo . H) / (ci sD^2)|   (mode EImportance: factor = 1),
+ *         dwh_dwo = eta^2 (wo . H) / sD^2
+ *       F = fresnelDielectricExt(wi . H, eta) (libcore/util.cpp:659-689; wi . H > 0 in wi's frame; total internal reflection: 1),
+ *       D = MicrofacetDistribution::eval(H) (microfacet.h:191-232), G = smithG1(wi, H) smithG1(wo, H) with signed cosines
+ *       (:477-522: dot(v, m) cosTheta(v) <= 0 gives 0),
+ *       pdf = |prob dwh_dwo| (reflection: F, transmission: 1 - F)                                                   (:350-422)
+ *         prob = D smithG1(wi, H) |wi . H| / ci  [sample_visible]   or   D' cos(theta_H), D' = the distribution at alpha scaled by
+ *         1.2 - 0.2 sqrt(ci) (:406-414), with its own D' cos(theta_H) < 1e-20 -> 0 cut.
+ *     D == 0 gives eval = 0, and pdf = 0 with visible normals; without them the pdf is D''s (RoughDielectric::pdf does not look at
+ *     D): a half vector between the two cuts is a shift that succeeds with zero flux.  The same holds where G = 0 (a direction no
+ *     facet reaches, a facet seen from behind): eval = 0, pdf > 0.  |wi + wo eta|^2 < 1e-12 (no half vector) is a failed shift.
+ *     Fields: `specular` = m_specularReflectance, k[0..2] = m_specularTransmittance (both after ensureEnergyConservation),
+ *     `exponent` = alpha (>= 1e-4), `distribution`, `sample_visible` as for the rough conductor, eta[0] as above; eta[1], eta[2],
+ *     `specular_sampling_weight` and `reserved` zero.  No raw entries behind the head.  gvpm_upload_bsdfs refuses, before anything
+ *     is copied (GVPM_ERR_INVALID_ARG): alpha < 1e-4, eta[0] not finite or outside [0.2, 5], a reflectance or transmittance
+ *     channel outside [0, 1], a non-zero word where zero is asked; GVPM_ERR_UNSUPPORTED: a distribution that is not Beckmann or GGX.
+ *   A record of any OTHER kind with cos(theta_i) <= 0 fails its shift, as ever.
  * A surface parent outside the closed set stays what it was: the host flags the photon's shift type 0 (failed shift).   */
 enum { GVPM_BSDF_PHONG = 1, GVPM_BSDF_ROUGHCONDUCTOR = 2, GVPM_BSDF_WARD = 3, GVPM_BSDF_ROUGHPLASTIC = 4, GVPM_BSDF_PLASTIC = 5,
-       GVPM_BSDF_WARD_ANISO = 6, GVPM_BSDF_ROUGHCONDUCTOR_ANISO = 8 };
+       GVPM_BSDF_WARD_ANISO = 6, GVPM_BSDF_ROUGHCONDUCTOR_ANISO = 8, GVPM_BSDF_ROUGHDIELECTRIC = 9 };
 #define GVPM_ANISO_ENTRIES 1           /* raw table entries behind an anisotropic head (the frame entry)            */
 #define GVPM_RTRANS_KNOTS 100          /* values of a rough-plastic slice                                          */
 #define GVPM_RTRANS_ENTRIES 7          /* raw table entries behind a rough-plastic head (448 bytes)                */
@@ -278,7 +314,8 @@ typedef struct gvpm_bsdf {    /* 64 bytes */
   int32_t distribution;       /* rough conductor: GVPM_MICROFACET_*; Phong: sampled component + 1 (0 = both) */
   int32_t sample_visible;     /* rough conductor: m_sampleVisible (the pdf's form); Ward: GVPM_WARD_* variant */
   float eta[3], k[3];         /* rough conductor: m_eta, m_k (relative to the exterior, roughconductor.cpp:181-191);
-                                 plastics: eta[0] = eta, eta[1] = Fdr, k[0] = component met (0 / 1 / 2), k[1] = nonlinear */
+                                 plastics: eta[0] = eta, eta[1] = Fdr, k[0] = component met (0 / 1 / 2), k[1] = nonlinear;
+                                 rough dielectric: eta[0] = relative index seen from wi's side, k = m_specularTransmittance */
   float reserved[2];
 } gvpm_bsdf;
 

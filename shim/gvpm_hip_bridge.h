@@ -453,7 +453,17 @@ private:
     push3(m_soa.parent_pos, par->getPosition());                     /* parentVertex->getPosition(), :389-395      */
     /* geometric normal of a surface / emitter parent (:404-412; area.cpp:132-150 for the emitter's cosine);
      * the closed set is Lambertian: shading frame = geometric frame                                                 */
-    push3(m_soa.parent_n, par->isMediumInteraction() ? Vector(0.f) : Vector(par->getGeometricNormal()));
+    /* ORDER MATTERS: glossyIndex() first.  For a plastic it records, in m_plasticFtr, the coating's diffuse transmittance that
+     * parent_scat is divided by below.  A plastic that plasticIndex() refuses (eta < 1, anisotropic, black) has no such
+     * record and keeps kd * Ftr: harmless, makeFlags() flags its shift type 0 and nothing reads its parent_scat.
+     * For a rough dielectric it tells that the record's normal must point to the side the path LEFT on -- towards
+     * vertex(c) -- (include/gvpm_hip.h, GVPM_BSDF_ROUGHDIELECTRIC): a transmitted photon flips it.                          */
+    const int glossy = glossyIndex(par);
+    Vector parentN = par->isMediumInteraction() ? Vector(0.f) : Vector(par->getGeometricNormal());
+    if (glossy >= 0 && m_bsdfs[(size_t) glossy].kind == GVPM_BSDF_ROUGHDIELECTRIC &&
+        dot(parentN, lt->vertex(c)->getPosition() - par->getPosition()) < 0)
+      parentN = -parentN;
+    push3(m_soa.parent_n, parentN);
     /* prod_{i < c-1} v_i.weight * v_i.rrWeight * e_i.weight, shift_volume_photon.cpp:415-422                        */
     Spectrum prefix(1.f);
     for (size_t i = 0; i + 1 < c; ++i)
@@ -461,10 +471,6 @@ private:
     push3(m_soa.prefix_w, prefix);
     /* BSDF::eval of the parent = diffuse reflectance * INV_PI * cos (src/bsdfs/diffuse.cpp:110-127);
      * medium parent: sigma_s * phase (shift_diffuse.cpp:54-70)                                                      */
-    /* ORDER MATTERS: glossyIndex() first.  For a plastic it records, in m_plasticFtr, the coating's diffuse transmittance that
-     * parent_scat is divided by below.  A plastic that plasticIndex() refuses (eta < 1, anisotropic, black) has no such
-     * record and keeps kd * Ftr: harmless, makeFlags() flags its shift type 0 and nothing reads its parent_scat.          */
-    const int glossy = glossyIndex(par);
     Spectrum scat(0.f);
     if (par->isSurfaceInteraction()) {
       const Intersection &its = par->getIntersection();
@@ -506,6 +512,7 @@ private:
     const std::string cls = bsdf->getClass()->getName();
     if (bsdf->getType() & BSDF::ESpatiallyVarying) return -1;
     if (cls == "RoughPlastic" || cls == "SmoothPlastic") return plasticIndex(par, its, bsdf, cls == "RoughPlastic");
+    if (cls == "RoughDielectric") return dielectricIndex(its, bsdf);
     if (cls != "Phong" && cls != "RoughConductor" && cls != "Ward") return -1;
     /* Ward (src/bsdfs/ward.cpp, round 5): isotropic (no EAnisotropic component: alphaU == alphaV, ward.cpp:144-146; the
      * anisotropic plugin goes to anisoIndex() below) and sampled with
@@ -712,6 +719,46 @@ private:
     m_bsdfsDirty = true;
     return (int) idx;
   }
+  /* RoughDielectric (src/bsdfs/roughdielectric.cpp; untextured -- the ESpatiallyVarying test above --, isotropic Beckmann or
+   * GGX): sampleComponent returns -1 at every roughness (:647-652), so there is no entry per component, but ONE PER SIDE OF
+   * INCIDENCE (include/gvpm_hip.h): keyed by the sign of parentIts.wi.z, eta[0] = m_eta = intIOR / extIOR (:190-196) where the
+   * light arrived on the outside (wi.z > 0), m_invEta where it arrived inside.  Reflectance and transmittance from the
+   * plugin's properties with its defaults (:184-187), scaled as ensureEnergyConservation does (src/librender/bsdf.cpp:102-120).
+   * The keys (BSDF, 2) and (BSDF, 3) stand apart from every sampled component index.                                      */
+  int dielectricIndex(const Intersection &its, const BSDF *bsdf) {
+    const bool inside = its.wi.z < 0;
+    const std::pair<const BSDF *, int> key(bsdf, inside ? 3 : 2);
+    auto found = m_bsdfIndex.find(key);
+    if (found != m_bsdfIndex.end()) return (int) found->second;
+    const Properties &props = bsdf->getProperties();
+    MicrofacetDistribution distr(props);
+    if (!distr.isIsotropic() || (distr.getType() != MicrofacetDistribution::EBeckmann && distr.getType() != MicrofacetDistribution::EGGX))
+      return -1;
+    const Float eta = lookupIOR(props, "intIOR", "bk7") / lookupIOR(props, "extIOR", "air");
+    if (!(eta >= 0.2f && eta <= 5.f)) return -1;   /* (gvpm_upload_bsdfs takes [0.2, 5] for either side)                    */
+    gvpm_bsdf b;
+    memset(&b, 0, sizeof(b));
+    b.kind = GVPM_BSDF_ROUGHDIELECTRIC;
+    b.exponent = (float) distr.getAlphaU();
+    b.distribution = distr.getType() == MicrofacetDistribution::EGGX ? GVPM_MICROFACET_GGX : GVPM_MICROFACET_BECKMANN;
+    b.sample_visible = distr.getSampleVisible() ? 1 : 0;
+    b.eta[0] = (float) (inside ? 1 / eta : eta);
+    Spectrum ks = props.getSpectrum("specularReflectance", Spectrum(1.0f)), kt = props.getSpectrum("specularTransmittance", Spectrum(1.0f));
+    if (props.getBoolean("ensureEnergyConservation", true)) {
+      if (ks.max() > 1) ks *= 0.99f / ks.max();
+      if (kt.max() > 1) kt *= 0.99f / kt.max();
+    }
+    Float cr, cg, cb;
+    ks.toLinearRGB(cr, cg, cb);
+    b.specular[0] = (float) cr; b.specular[1] = (float) cg; b.specular[2] = (float) cb;
+    kt.toLinearRGB(cr, cg, cb);
+    b.k[0] = (float) cr; b.k[1] = (float) cg; b.k[2] = (float) cb;
+    const uint32_t idx = (uint32_t) m_bsdfs.size();
+    m_bsdfs.push_back(b);
+    m_bsdfIndex[key] = idx;
+    m_bsdfsDirty = true;
+    return (int) idx;
+  }
   std::map<const BSDF *, Float> m_plasticFtr;   /* plastic BSDF -> the diffuse transmittance its getDiffuseReflectance carries */
   std::map<std::pair<const BSDF *, int>, uint32_t> m_bsdfIndex;   /* (BSDF, sampled component) -> table entry */
   std::vector<gvpm_bsdf> m_bsdfs;
@@ -732,7 +779,9 @@ private:
      * a rough conductor has one component and one entry, keyed with -1) */
     const bool glossy = parBsdf != nullptr &&
                         (m_bsdfIndex.count(std::make_pair(parBsdf, (int) par->sampledComponentIndex)) != 0 ||
-                         m_bsdfIndex.count(std::make_pair(parBsdf, -1)) != 0);
+                         m_bsdfIndex.count(std::make_pair(parBsdf, -1)) != 0 ||
+                         m_bsdfIndex.count(std::make_pair(parBsdf, par->getIntersection().wi.z < 0 ? 3 : 2)) != 0);   /* (a rough
+                                                                   dielectric: an entry per side of incidence, dielectricIndex()) */
     if (st == 1u || st == 2u) {
       if (par->isSurfaceInteraction() && !glossy) {
         const BSDF *bsdf = par->getIntersection().getBSDF();
