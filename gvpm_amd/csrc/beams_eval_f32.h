@@ -1,5 +1,5 @@
 // fp32 evaluation of one (camera ray, sub-beam) pair for the G-Beams kernels: the same functions as the fp64
-// transcription in gather_beams.hip (BeamKernelRecord, shiftNull3D, shiftBeamDiffuse, kernelPDF, getShiftPos*),
+// transcription in beams_eval_f64.h (BeamKernelRecord, shiftNull3D, shiftBeamDiffuse, kernelPDF, getShiftPos*),
 // re-derived in a LOCAL frame so that single precision is enough.
 //
 // Why a local frame.  The reference works on absolute coordinates (scene extent ~10^3, kernel radius ~1): the

@@ -416,7 +416,7 @@ struct gvpm_context {
   DevBuf<uint32_t> vpmCtl, vpmStatus, vpmRedo;
   DevBuf<VpmSampleState> vpmState;
   hipEvent_t vpmFound = nullptr, vpmRedone = nullptr;
-  // GVPM_BEAMS_SPLIT=1: the evaluation in two kernels (gather_beams.hip); the reconnection entries between them
+  // GVPM_BEAMS_SPLIT=1: the evaluation in two kernels (gather_beams_split.hip); the reconnection entries between them
   bool beamsSplit = false;
   DevBuf<uint32_t> splitId, splitMeta, splitBlkCnt, splitCtl;
   DevBuf<float4> splitK;

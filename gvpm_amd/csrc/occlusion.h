@@ -60,7 +60,7 @@ __device__ __forceinline__ int triHit3(const float4 t0, const float4 t1, const f
   const f3 v0 = mk3(t0.x, t0.y, t0.z), nrm = mk3(t0.w, t1.w, t2.w);
   return triHit3(v0, mk3(t1.x, t1.y, t1.z), mk3(t2.x, t2.y, t2.z), o, d, mint, maxt, oAbs1, dot(nrm, o - v0), dot(nrm, d));
 }
-// A second opinion on a triangle triHit3 left undecided (the G-Beams shadow segments, gather_beams.hip).  The division-free
+// A second opinion on a triangle triHit3 left undecided (the G-Beams shadow segments, beams_shift_f32.h).  The division-free
 // comparisons above bound the errors of A, B and C independently -- each carries |o - v0| |e|, the distance to the triangle's
 // FAR corner -- although an error of the direction moves A / C only by the lever from the origin to the crossing point.
 // Here the crossing point itself is formed, P = (o - v0) + d t with t = -s0 / sd, and tested against the edges in the

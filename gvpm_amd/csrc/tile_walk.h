@@ -1,4 +1,4 @@
-// Tile traversal shared by the beam-vs-point gather kernels (gather_bre.hip, gather_beams.hip):
+// Tile traversal shared by the beam-vs-point gather kernels (gather_bre.hip, gather_beams_trav.hip and the G-Beams evaluation units):
 // LDS layout of a tile of camera-beam sets, the slab walk over the sorted uniform grid and the
 // planner that cuts tiles into work items of equal candidate count.  See gather_bre.hip.
 #pragma once

@@ -1,5 +1,5 @@
 """Probe: audit of the fp32 kernel record of the G-Beams evaluation against the fp64 transcription, pair by pair
-(needs the variant: bash scripts/build_variant.sh baudit gather_beams.hip -DGVPM_BEAMS_AUDIT).
+(needs the variant: bash scripts/build_variant.sh baudit gather_beams.hip -DGVPM_BEAMS_AUDIT; the reader of the log is in that unit).
 python scripts/beams_audit.py [beams_bench args]"""
 import ctypes
 import os

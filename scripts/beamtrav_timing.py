@@ -1,5 +1,5 @@
 """Probe: the persistent waves of traverse_beams_kernel in time (last launch; needs the variant
-  bash scripts/build_variant.sh ttiming gather_beams.hip -DGVPM_TRAV_TIMING).  python scripts/beamtrav_timing.py [beams_bench args]"""
+  bash scripts/build_variant.sh ttiming gather_beams_trav.hip -DGVPM_TRAV_TIMING).  python scripts/beamtrav_timing.py [beams_bench args]"""
 import ctypes, os, runpy, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lib = os.path.join(ROOT, "build", "variants", "libgvpm_hip_ttiming.so")

@@ -1,5 +1,7 @@
 """Find the (camera set, beam) pair on which the device's G-Beams shift counters differ from the oracle's: bisection over the
-camera sets, then over the beams.  python scripts/probes_py/beams_bisect.py scene tech scale [free_cone]   (GPU box)"""
+camera sets, then over the beams.  python scripts/probes_py/beams_bisect.py scene tech scale [free_cone]   (GPU box)
+With the variant  bash scripts/build_variant.sh dbg2 gather_beams.hip -DGVPM_DBG_SHIFT2  (the macro is in beams_shift_f32.h; the
+default evaluation includes it) the pair found is run once more through that library."""
 import os, sys
 sys.path.insert(0, "tests"); sys.path.insert(0, ".")
 import numpy as np

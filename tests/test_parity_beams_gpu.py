@@ -40,7 +40,7 @@ def device_beams(c, p=None, rays=None, iters=1, exact=True):
     lum = max(ref[..., 0:3].mean(), 1e-30)
     # "count = device atomic, must equal the oracle's count exactly" -- on the default (fp32 local-frame)
     # path too: every validity decision of the kernel record is banded and settled in fp64 inside the band
-    # (gather_beams.hip beamBase / beamKernelExact).  Round 5: the shifts' own decisions (null shift or reconnection, the
+    # (beams_shift_f32.h beamBase / beamKernelExact).  Round 5: the shifts' own decisions (null shift or reconnection, the
     # visibility of a reconnection) are banded as well and the undecided shifts evaluated in fp64 behind the kernel
     # (exact_beams_kernel): the shift counters are exact too (exact=False: the +-2 of rounds 1-4, for callers that feed
     # the device something the oracle does not see bit for bit).

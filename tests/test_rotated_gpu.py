@@ -105,7 +105,7 @@ def test_vpm(scene, vis):
 @pytest.mark.parametrize("scene", ["cbox_rot", "cbox_hg_rot", "laser_rot", "cbox_conductor_rot", "cbox_phong1_rot", "cbox_ward_rot"])
 def test_beams(tech, scene):
     c = make_beam_case(scene, 32, 28, 12000, 1.6, technique=tech)
-    # (G-Beams: the shifts' decisions are banded too -- gather_beams.hip beamShift1 / beamShift2 -- and the undecided ones go to
+    # (G-Beams: the shifts' decisions are banded too -- beams_shift_f32.h beamShift1 / beamShift2 -- and the undecided ones go to
     # exact_beams_kernel behind the evaluation)
     acc, ref, st = device_beams(c, exact=True)
     assert st["evaluations"] > 10000
