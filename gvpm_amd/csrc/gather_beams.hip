@@ -426,7 +426,11 @@ __global__ __launch_bounds__(64, 1) void evaluate_beams_exact_kernel(GatherArgs 
       const uint2 e = pairs[(size_t)sortedBlock[bi] * 64u + lane];
       const bool live = e.x != 0xFFFFFFFFu && e.y >= setBase && e.y - setBase < curNb;
       if (live) {
-        if (evaluateBeam<B>(a, s, e.x, e.y - setBase, nNull, nDiff, nFail)) nEval++;
+        // (EXV: the shadow segments through anyHitExact, every triangle test in fp64 as the exact pass takes them.  With the plain
+        // fp32 test the cross-check was literal only where no parent self-hits: in a room 256 wide 1400 from the origin, Epsilon
+        // at the ulp of a coordinate, 34 of 145 000 shifts went the other way -- found by the `centimetres` transform,
+        // tests/test_similarity_gpu.py)
+        if (evaluateBeam<B, true>(a, s, e.x, e.y - setBase, nNull, nDiff, nFail)) nEval++;
       }
     }
     flushTile();

@@ -533,7 +533,11 @@ __device__ __forceinline__ void evalPhase2Core(const GatherArgs &a, LDS &s, uint
   }
   bool ok = false;
   f3 sflux;
-  const f3 dProjU = ((basePt + dS) - ph.parentPos) + offRel;  // offsetPos - parent
+  // offsetPos - parent is a difference of two ABSOLUTE positions: baseRay(t') - parent is formed from the difference of the
+  // two fp32 origins (one rounding, relative to the DIFFERENCE), never through the fp32 point basePt, whose rounding is half an
+  // ulp of a COORDINATE -- 1e-7 of the unit room, but 1e-4 of a reconnection 2000 units from the origin: the film's L2 at
+  // 1.4e-4 and two cosine tests at a Phong wall decided differently (found by the `far` transform, tests/test_similarity_gpu.py)
+  const f3 dProjU = (((base.o - ph.parentPos) + base.d * (float)tPrime) + dS) + offRel;
   uint32_t ambVis = 0u;
   float w = shiftDiffuse<FULLVIS>(a, ph, ph.bits, dProjU, sh, base, s.edge[b], trT, pdfCam, pdfShiftPos, sflux, ok, ldsTri,
                                  sr.sMIS, &ambVis);

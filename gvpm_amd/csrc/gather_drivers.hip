@@ -1054,7 +1054,7 @@ static int gatherBeams(gvpm_context *h, int it, uint64_t nb_paths, bool primal =
   if (nearDirty || h->beamNearStale) {
     HIP_TRY(h, h->shiftExtent.ensure(1));
     HIP_TRY(h, h->beamClear.ensure((size_t)h->nph + 1));
-    launch_beam_near(h->bs->cold.p, h->nph, h->tri4.p, h->ntri, r, h->shiftExtent.p, h->beamClear.p, h->beamsFreeCone, h->stream);
+    launch_beam_near(h->bs->cold.p, h->nph, h->tri4.p, h->ntri, r, h->cfg.epsilon, h->shiftExtent.p, h->beamClear.p, h->beamsFreeCone, h->stream);
     if (getenv("GVPM_BEAMS_TRACE")) {
       DevBuf<uint32_t> hist;
       uint32_t hh[21] = {0}, ext = 0;

@@ -320,7 +320,10 @@ __device__ __forceinline__ void vpmPhase2(const GatherArgs &a, LDS &s, uint32_t 
     }
     return;
   }
-  const f3 dProjU = (tof(zP) - v.ph.parentPos) + offRel;
+  // (offsetPos - parent from the DIFFERENCE of the two fp32 positions, one rounding relative to that difference: through the fp32
+  // point tof(zP) it was half an ulp of a COORDINATE, 1e-4 of a reconnection 2000 units from the origin -- found by the `far`
+  // transform, tests/test_similarity_gpu.py)
+  const f3 dProjU = ((sh.o - v.ph.parentPos) + sh.d * v.tf) + offRel;
   bool ok = false;
   f3 sflux = mk3(0.f);
   uint32_t ambVis = 0u;

@@ -757,7 +757,7 @@ __global__ __launch_bounds__(256) void shift_extent_kernel(const gvpm_camera_ray
 struct BeamClearTri {
   float cosT, alongMin;
 };
-__device__ __forceinline__ BeamClearTri beamClearTri(const float p1[3], const float bd[3], float delta, const float4 t0, const float4 t1,
+__device__ __forceinline__ BeamClearTri beamClearTri(const float p1[3], const float bd[3], float delta, float eps, const float4 t0, const float4 t1,
                                                      const float4 t2) {
   const float a[3] = {t0.x - p1[0], t0.y - p1[1], t0.z - p1[2]};
   const float e1[3] = {t1.x, t1.y, t1.z}, e2[3] = {t2.x, t2.y, t2.z};
@@ -788,15 +788,22 @@ __device__ __forceinline__ BeamClearTri beamClearTri(const float p1[3], const fl
   // the beam's line through the triangle (Moeller-Trumbore from p1 along bd, with slack: a near miss is a hit here)
   const float nrm[3] = {t0.w, t1.w, t2.w};
   const float cn = dot3(bd, nrm), dn = dot3(a, nrm);  // plane: nrm . (x - v0) = 0, a = v0 - p1
-  // The wall the beam STARTS on (p1 within position rounding of the plane; round 5): p1 may lie a few 1e-7 BEHIND it, and a
-  // new beam within |delta| / Epsilon (~ 4e-3 rad) of grazing then meets the plane at t >= Epsilon -- the reference's
-  // rayIntersect reports that hit (shift_volume_beams.cpp:420-426).  The cone such a wall leaves free is drawn 0.02 rad
-  // inside its plane: reconnections in the sliver take the any-hit loop, where triHitChecked decides them in fp64.
+  // The wall the beam STARTS on (p1 within position rounding of the plane; round 5): p1 may lie |delta| BEHIND it, and a new beam
+  // whose cosine to the normal is below |delta| / Epsilon then meets the plane at t = |delta| / cos >= Epsilon -- the reference's
+  // rayIntersect reports that hit (shift_volume_beams.cpp:420-426).  The cone such a wall leaves free is drawn inside its plane
+  // by that reach, taken from what is known of delta here: |dn| plus the rounding of dn (the fp32 difference a = v0 - p1 and the
+  // stored unit normal: 5e-7 |a|_1), times 1.5.  In the unit room that is the 0.02 rad this sliver used to be as a constant
+  // (|delta| a few 1e-7, Epsilon 1e-4); a room 256 wide 1400 from the origin has |delta| ~ Epsilon and NO direction is free of
+  // its own wall -- the constant certified reconnections there that self-hit in the reference (found by the `centimetres`
+  // transform, tests/test_similarity_gpu.py: 15 of 145 000 shifts).  Reconnections in the sliver take the any-hit loop, whose
+  // undecided triangles go to the exact pass.
   {
     const float scale = fabsf(p1[0]) + fabsf(p1[1]) + fabsf(p1[2]) + fabsf(t0.x) + fabsf(t0.y) + fabsf(t0.z);
     if (fabsf(dn) <= 2e-6f * (1.f + scale) && o.cosT < 1.f) {
+      const float a1 = fabsf(a[0]) + fabsf(a[1]) + fabsf(a[2]);
+      const float sinS = 1.5f * (fabsf(dn) + 5e-7f * a1) / eps;
       const float sinT = sqrtf(fmaxf(1.f - o.cosT * o.cosT, 0.f));
-      o.cosT = fminf(1.f, o.cosT * 0.9998f + sinT * 0.02f);  // cos(angle - 0.02)
+      o.cosT = sinS < 1.f ? fminf(1.f, o.cosT * sqrtf(1.f - sinS * sinS) + sinT * sinS) : 1.f;  // cos(angle - asin(sinS))
     }
   }
   o.alongMin = -INFINITY;
@@ -823,7 +830,7 @@ __device__ __forceinline__ BeamClearTri beamClearTri(const float p1[3], const fl
 }
 
 __global__ __launch_bounds__(128) void beam_near_kernel(float4 *cold, uint32_t n, const float4 *__restrict__ tri4, uint32_t ntri,
-                                                        float r, const uint32_t *__restrict__ extentBits, float2 *clear, bool freeCone) {
+                                                        float r, float eps, const uint32_t *__restrict__ extentBits, float2 *clear, bool freeCone) {
   __shared__ float2 ctab[19][128];  // (19: the longest list, BeamNearFmt)
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -895,7 +902,7 @@ __global__ __launch_bounds__(128) void beam_near_kernel(float4 *cold, uint32_t n
       for (uint32_t q = 0; q < fmt.cap; ++q) {
         const uint32_t t = beamNearEntry(fmt, w[0], w[1], w[2], q);
         if (t == fmt.mask) break;
-        const BeamClearTri ct = beamClearTri(p1, bd, delta, tri4[3 * t], tri4[3 * t + 1], tri4[3 * t + 2]);
+        const BeamClearTri ct = beamClearTri(p1, bd, delta, eps, tri4[3 * t], tri4[3 * t + 1], tri4[3 * t + 2]);
         ctab[q][threadIdx.x] = make_float2(ct.cosT, ct.alongMin);
         nl = q + 1;
         if (ct.cosT > cosSmall) M1 = fminf(M1, ct.alongMin);
@@ -934,9 +941,9 @@ __global__ __launch_bounds__(256) void beam_near_hist_kernel(const float4 *__res
 void launch_beam_near_hist(const float4 *cold, uint32_t n, uint32_t ntri, uint32_t *hist, hipStream_t s) {
   if (n) hipLaunchKernelGGL(beam_near_hist_kernel, dim3((n + 255) / 256), dim3(256), 0, s, cold, n, ntri, hist);
 }
-void launch_beam_near(float4 *cold, uint32_t n, const float4 *tri4, uint32_t ntri, float r, const uint32_t *extentBits,
+void launch_beam_near(float4 *cold, uint32_t n, const float4 *tri4, uint32_t ntri, float r, float eps, const uint32_t *extentBits,
                       float2 *clear, bool freeCone, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(beam_near_kernel, dim3((n + 127) / 128), dim3(128), 0, s, cold, n, tri4, ntri, r, extentBits, clear, freeCone);
+  if (n) hipLaunchKernelGGL(beam_near_kernel, dim3((n + 127) / 128), dim3(128), 0, s, cold, n, tri4, ntri, r, eps, extentBits, clear, freeCone);
 }
 
 void launch_beam_cold(const gvpm_photon_soa &raw, const float *endN, uint32_t n, const gvpm_params &cfg,

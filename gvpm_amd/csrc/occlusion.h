@@ -108,7 +108,8 @@ __device__ __forceinline__ int triCombine(int acc, int t) {
   return (acc | t) & GVPM_TRI_AMB;
 }
 // the plain fp32 test (branch-free: the tests of the reference are and-ed; a zero determinant gives inf / NaN, which fail
-// the comparisons like the early return): what the literal fp64 cross-check of G-Beams (GVPM_BEAMS_FP64) walks the scene with
+// the comparisons like the early return): probe builds' plain visibility (GVPM_PROBE_PLAINVIS); the literal fp64 cross-check of
+// G-Beams (GVPM_BEAMS_FP64) walked the scene with it until its shadow segments went to anyHitExact
 __device__ __forceinline__ bool triHit(f3 v0, f3 e1, f3 e2, f3 o, f3 d, float mint, float maxt) {
   const f3 pvec = cross(d, e2);
   const float det = dot(e1, pvec);
