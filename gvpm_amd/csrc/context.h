@@ -1,6 +1,8 @@
 // Internal to libgvpm_hip.so: the handle behind the C ABI (include/gvpm_hip.h), its device buffers and the launch functions of
 // the kernel files.  Shared by gvpm_api.hip (lifecycle, results, comm), uploads.hip (staging of the per-iteration inputs)
-// and gather_drivers.hip (the per-technique drivers behind gvpm_gather).
+// and the host-only driver units behind gvpm_gather: gather_drivers.hip (entry, shared helpers, G-Planes, host shifts),
+// drivers_build.hip (photon grid, beam sort), drivers_bre.hip, drivers_beams.hip and drivers_vpm.hip (drivers.h declares
+// what they share).
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -183,6 +185,8 @@ struct RcclApi {
 extern RcclApi g_rccl;
 
 #define GVPM_PHASES 3
+// gvpm_context::trace: GVPM_TRACE_HOST, GVPM_TRACE_PLAN, GVPM_TRACE_VIS, GVPM_TRACE_EXACT, GVPM_BEAMS_TRACE
+enum : uint32_t { TRACE_HOST = 1u, TRACE_PLAN = 2u, TRACE_VIS = 4u, TRACE_EXACT = 8u, TRACE_BEAMS = 16u };
 // counters: GVPM_STAT_ROWS rows of 8 (device_types.h), one per persistent wave / a few workgroups each, summed on read
 
 // Everything a gather reads that is rebuilt per photon set / beam set.  Two of them: G-BRE builds
@@ -255,21 +259,13 @@ struct gvpm_context {
   hipStream_t streamB = nullptr;  // build stream of the G-BRE pipeline
   hipStream_t bstream = nullptr;  // where the current gather builds (stream, or streamB for G-BRE)
   hipStream_t streamC = nullptr;  // traversal stream of the three-stage pipeline
-  // G-BRE (round 6): consecutive evaluations on ALTERNATING streams (`stream`, `streamA2`).  They read different build sets and
-  // add to the running sums with atomics, so nothing orders them but the stream -- and on one stream the next evaluation
-  // waited for the last wave of this one (a third of a launch is its tail) plus two kernel boundaries around capture_notes.
-  // Everything that reads or rescales the sums joins both first (gvpm_join_exact).  GVPM_EVAL_ALT=0: one stream.
+  // a second gather-side stream: G-VPM's redo of the heavy batches runs on it beside the evaluation (gatherVPM).  (Round 6 also
+  // alternated G-BRE's evaluations between it and `stream`: 1.10-1.12 ms a C2 step either way, so they stay on `stream`.)
   hipStream_t streamA2 = nullptr;
-  bool evalAlt = false;  // (measured at C2, round 6: 1.10-1.12 ms a step either way -- each evaluation then takes 1.4 ms beside the next instead of 1.0 alone)
-  int evalToggle = 0;
-  hipEvent_t exactDone = nullptr;  // behind the last exact pass (gather stream)
-  bool exactDoneValid = false;
-  hipStream_t lastEvalStream = nullptr;  // where the last gather's evaluation went (its camera rays are read until it ends)
-  bool travStream = true;         // traversal on its own stream, three build sets (GVPM_TRAV_STREAM=0: two stages)
+  bool travStream = true;         // traversal on its own stream, three build sets (GVPM_TRAV_STREAM=0: two stages, traversal on the build stream)
   BuildSet sets[3];
   BuildSet *bs = &sets[0];
   int setIdx = 0;
-  bool travOnBuild = true;        // traversal on the build stream (else on the gather stream)
   bool beamsExact = false;        // G-Beams: the literal fp64 evaluation instead of the local-frame fp32 one
   // G-BRE bundle cells (Grid::mode 1, bundle_grid.h), GVPM_BUNDLE=1.  Off by default: measured on MI355X (round 3,
   // scripts/r03_bundle_ab.sh, r03_bundle_c4.sh) the traversal gains 16 % alone (0.45 -> 0.38 ms at C2) and a rank's step
@@ -295,6 +291,7 @@ struct gvpm_context {
   uint32_t beamItemsInit = 0;     // G-Beams: first capacity of the item list (GVPM_BEAM_ITEMS_INIT; tests shrink it; 0: the planner's bound)
   uint32_t beamItemCap = 0;       // G-Beams: capacity the item list was regrown to after an overflow
   bool pipeline = true;           // GVPM_PIPELINE=0: everything on the gather stream (isolated kernel timings)
+  uint32_t trace = 0;             // TRACE_* bits: the host-side traces on stderr, read from the environment at gvpm_create
   gvpm_params cfg;
   gvpm_medium medium;
   bool haveMedium = false;

@@ -1506,7 +1506,7 @@ void launch_traverse_bre(const GatherArgs &a, int beamsPerWave, const uint4 *ite
 #define GVPM_LAUNCH_TRAV(BB, OWN) \
   hipLaunchKernelGGL((traverse_bre_kernel<BB, OWN>), grid, block, 0, stream, a, items, itemOff, itemCount, queueHead, pairs, pairCnt, \
                      persist, units, unitCtl, unitCap)
-  // (the driver hands the planner's boxes over whenever it can size them, gather_drivers.hip)
+  // (the driver hands the planner's boxes over whenever it can size them, drivers_bre.hip)
   const bool own = a.planBoxes == nullptr;
   switch (beamsPerWave) {
     case 64: if (own) GVPM_LAUNCH_TRAV(64, true); else GVPM_LAUNCH_TRAV(64, false); break;

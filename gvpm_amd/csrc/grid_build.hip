@@ -1187,7 +1187,7 @@ __global__ __launch_bounds__(256) void chain_count_kernel(ChainArgs c) {
   } else {
     // the beam sets: key = tile * tilePixels + pixel in tile, counted behind the cells (the sets of one pixel -- one per
     // medium edge of its camera path -- keep no order among themselves: nothing reads one).  Their base rays' segments give
-    // the region the NEXT build's grid is clipped to (gather_drivers.hip, buildGrid).
+    // the region the NEXT build's grid is clipped to (drivers_build.hip, buildGrid).
     const uint32_t i = (b - c.nPhBlocks) * 256u + threadIdx.x;
     if (i < c.nsets) {
       const gvpm_camera_ray &r = c.rays[(size_t)i * 5];
@@ -1389,7 +1389,7 @@ struct TailArgs {
   uint32_t *ctl;
   const uint32_t *bundleFlag;
   uint32_t *hostOut;
-  // The guard of an OPTIMISTIC step (gather_drivers.hip, gatherBRE): traversal and evaluation are queued behind this launch
+  // The guard of an OPTIMISTIC step (drivers_bre.hip, gatherBRE): traversal and evaluation are queued behind this launch
   // before the host has seen its counters, sized for what the buffers hold.  The last block compares and leaves a status in
   // itemCount[7]; non-zero, both kernels return at once and the host, which reads the same word, queues them again.
   uint32_t pairCapBlocks;  // 64-entry blocks the pair buffer holds (0xFFFFFFFF: not optimistic, no guard)

@@ -135,7 +135,6 @@ int gvpm_create(const gvpm_params *params, int device, gvpm_context **out) {
   // build of the following steps 8 per CU leave them room (measured: 12 per CU costs the pipelined step 3-4 %)
   if (!h->pipeline && !getenv("GVPM_WAVES_PER_CU") && h->ncu) h->nwaves = std::min<uint32_t>(h->ncu * 12u, GVPM_STAT_ROWS);
   if (const char *e = getenv("GVPM_PERSISTENT")) h->persistentEval = (atoi(e) & 1) != 0, h->persistentTrav = (atoi(e) & 2) != 0;
-  if (const char *e = getenv("GVPM_TRAV_ON_BUILD")) h->travOnBuild = atoi(e) != 0;
   if (const char *e = getenv("GVPM_NEAR_GRID")) h->useNearGrid = atoi(e) != 0;
   if (const char *e = getenv("GVPM_TRAV_STREAM")) h->travStream = atoi(e) != 0;
   if (const char *e = getenv("GVPM_BEAMS_FP64")) h->beamsExact = atoi(e) != 0;
@@ -146,7 +145,11 @@ int gvpm_create(const gvpm_params *params, int device, gvpm_context **out) {
   if (const char *e = getenv("GVPM_OPTIMISTIC")) h->optimistic = atoi(e) != 0;
   if (const char *e = getenv("GVPM_OPTIMISTIC_REFUSE")) h->optRefuseEvery = (uint32_t)std::max(0, atoi(e));
   if (const char *e = getenv("GVPM_CLIP_GRID")) h->clipGrid = atoi(e) != 0;
-  if (const char *e = getenv("GVPM_EVAL_ALT")) h->evalAlt = atoi(e) != 0;
+  if (getenv("GVPM_TRACE_HOST")) h->trace |= TRACE_HOST;
+  if (getenv("GVPM_TRACE_PLAN")) h->trace |= TRACE_PLAN;
+  if (getenv("GVPM_TRACE_VIS")) h->trace |= TRACE_VIS;
+  if (getenv("GVPM_TRACE_EXACT")) h->trace |= TRACE_EXACT;
+  if (getenv("GVPM_BEAMS_TRACE")) h->trace |= TRACE_BEAMS;
   if (const char *e = getenv("GVPM_VPM_ORDER")) h->vpmNoOrder = atoi(e) == 0;
   if (const char *e = getenv("GVPM_VPM_SPLIT")) h->vpmSplit = atoi(e) != 0;
   if (const char *e = getenv("GVPM_VPM_PIPELINE")) h->vpmPipeline = atoi(e) != 0;
@@ -254,7 +257,6 @@ int gvpm_destroy(gvpm_context *h) {
   if (h->streamB) (void)hipStreamDestroy(h->streamB);
   if (h->streamC) (void)hipStreamDestroy(h->streamC);
   if (h->streamA2) (void)hipStreamDestroy(h->streamA2);
-  if (h->exactDone) (void)hipEventDestroy(h->exactDone);
   h->vpmPairs.release(); h->vpmChunkMeta.release(); h->vpmCtl.release(); h->vpmStatus.release(); h->vpmRedo.release(); h->vpmState.release();
   if (h->vpmFound) (void)hipEventDestroy(h->vpmFound);
   if (h->vpmRedone) (void)hipEventDestroy(h->vpmRedone);
@@ -507,17 +509,18 @@ int gvpm_get_exact_shift_count(gvpm_context *h, uint64_t *evaluated, uint64_t *l
   // (the cause slots 4.. are a bit MASK's bits for G-BRE / G-VPM, exact_pass_kernel, and a cause NUMBER 0..9 for
   // G-Beams, exact_beams_kernel -- the same slots, so each technique's line is printed under its own labels)
   const bool beamsTech = h->cfg.vol_technique == GVPM_BEAM_BEAM_1D || h->cfg.vol_technique == GVPM_BEAM_BEAM_3D_OPTIMIZED;
-  if (getenv("GVPM_TRACE_EXACT") && beamsTech) {
+  const bool trace = (h->trace & TRACE_EXACT) != 0;
+  if (trace && beamsTech) {
     fprintf(stderr, "[exact beams] evaluated %llu lost %llu largest list %llu; by cause number 0..9:", v[0], v[1], v[2]);
     for (int k = 0; k < 10; ++k) fprintf(stderr, " %llu", v[4 + k]);
     fprintf(stderr, "\n");
-  } else if (getenv("GVPM_TRACE_EXACT"))
+  } else if (trace)
     fprintf(stderr, "[exact] evaluated %llu lost %llu largest list %llu; by cause: pair %llu branch %llu mirror %llu visibility %llu cosine %llu\n",
             v[0], v[1], v[2], v[4], v[5], v[7], v[8], v[9]);
-  if (getenv("GVPM_TRACE_EXACT") && !beamsTech && (v[16] | v[17] | v[18] | v[19] | v[20]))
+  if (trace && !beamsTech && (v[16] | v[17] | v[18] | v[19] | v[20]))
     fprintf(stderr, "[exact] visibility-caused, |cos| < .01 / .03 / .1 / .3 / more: surface parents %llu %llu %llu %llu %llu, medium parents %llu %llu %llu %llu %llu\n",
             v[16], v[17], v[18], v[19], v[20], v[21], v[22], v[23], v[24], v[25]);
-  if (getenv("GVPM_TRACE_EXACT") && !beamsTech && (v[10] | v[11] | v[12] | v[13]))
+  if (trace && !beamsTech && (v[10] | v[11] | v[12] | v[13]))
     fprintf(stderr, "[exact] pairs: other %llu, rim of the kernel %llu, beyond the beam's end %llu, t' at an end %llu\n", v[10], v[11], v[12], v[13]);
   if (evaluated) *evaluated = v[0];
   if (lost) *lost = v[1];

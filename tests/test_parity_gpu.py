@@ -591,3 +591,43 @@ def test_optimistic_step_refused_by_the_build_is_queued_again(monkeypatch):
         ev += cnt["evaluations"]
     assert st1["evaluations"] == ev
     assert l2(acc1, ref, max(ref[..., 0:3].mean(), 1e-30)) < TOL
+
+
+@pytest.mark.parametrize("variant", ["replan", "bre2d", "GVPM_TRAV_STREAM=0", "GVPM_PIPELINE=0", "GVPM_BUILD_CHAIN=0"])
+def test_step_variants_that_no_other_test_reaches(variant, monkeypatch):
+    """Branches of the G-BRE step (drivers_bre.hip) outside every other test's way, two iterations each against the
+    oracle's fold: the same photons, beams and radius again (alpha = 1, nothing uploaded in between), which re-plans the
+    built set in place with the planner as its own launch; a second BRE2D step, whose radius took the square-root
+    exponent of scaleVolumeAPA; the two-stage pipeline, whose traversal runs on the build
+    stream; everything on the gather stream; and the build as separate launches instead of the chain."""
+    replan, knob = variant == "replan", "=" in variant
+    kw = dict(vol_technique=abi.GVPM_VOL_BRE2D, use_shift_null=0) if variant == "bre2d" else {}
+    c = cases.make_case("cbox", 24, 20, 8000, 3.0, **kw)
+    p = c.p.copy()
+    if replan:
+        p.alpha = 1.0
+    if knob:
+        monkeypatch.setenv(*variant.split("="))
+    ctx = hip.Context(p, device=0)
+    if knob:
+        monkeypatch.delenv(variant.split("=")[0])
+    ctx.upload_scene(*c.tris)
+    ctx.upload_medium(c.m)
+    ref, ev, scale = None, 0, p.initial_scale_volume
+    for it in (1, 2):
+        if it == 1 or not replan:
+            ph, nb = c.sc.shoot_photons(it, 8000)
+            rays = c.sc.camera_beams(it)
+            ctx.upload_photons(ph)
+            ctx.upload_camera_beams(rays)
+        r = ctx.radius()
+        assert r == cases.radius_of(p, np.float32(scale)) and (not replan or r == c.r)
+        ctx.gather(it, nb)
+        ref, cnt, _ = O.gather_bre(p, c.m, c.tris, ph, rays, r, it, nb, 64, use_accel=False, accum=ref)
+        ev += cnt["evaluations"]
+        scale = np.float32(O.scale_volume_apa(float(scale), it, float(p.alpha), p.vol_technique))
+    acc = ctx.download_accum()
+    st = ctx.stats()
+    ctx.close()
+    assert st["evaluations"] == ev > 1000
+    assert l2(acc, ref, max(ref[..., 0:3].mean(), 1e-30)) < TOL
