@@ -177,6 +177,7 @@ def bsdf_tail_entries(kind):
 
 GVPM_WARD_WARD, GVPM_WARD_DUER, GVPM_WARD_BALANCED = 0, 1, 2
 GVPM_MICROFACET_BECKMANN, GVPM_MICROFACET_GGX = 0, 1
+GVPM_MICROFACET_PHONG = 3  # (2 is not a distribution: include/gvpm_hip.h)
 
 
 def rtrans_entries(values):

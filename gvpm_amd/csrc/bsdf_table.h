@@ -50,8 +50,10 @@ GVPM_TBL bool bsdfTailWordValid(int kind, int j, float v) {
 GVPM_TBL bool bsdfWeightValid(float w) { return w >= 0.f && w <= 1.f; }
 GVPM_TBL bool bsdfAlphaValid(float alpha) { return alpha >= 1e-4f; }  // (the microfacet constructor's clamp, microfacet.h:88-90)
 GVPM_TBL bool bsdfMicrofacetValid(const gvpm_bsdf &b) {
-  return b.distribution == GVPM_MICROFACET_BECKMANN || b.distribution == GVPM_MICROFACET_GGX;
+  return b.distribution == GVPM_MICROFACET_BECKMANN || b.distribution == GVPM_MICROFACET_GGX || b.distribution == GVPM_MICROFACET_PHONG;
 }
+// (the Phong / Ashikhmin-Shirley distribution has no visible-normal sampling: the reference forces it off, microfacet.h:140-144)
+GVPM_TBL bool bsdfSampleVisibleValid(const gvpm_bsdf &b) { return b.distribution != GVPM_MICROFACET_PHONG || b.sample_visible == 0; }
 // (Ward: the variant rides in sample_visible, and both components only)
 GVPM_TBL bool bsdfWardVariantValid(const gvpm_bsdf &b) {
   return b.sample_visible >= GVPM_WARD_WARD && b.sample_visible <= GVPM_WARD_BALANCED && b.distribution == 0;

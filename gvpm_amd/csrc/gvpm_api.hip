@@ -420,13 +420,16 @@ static int checkBsdf(gvpm_context *h, const gvpm_bsdf *table, uint32_t i, uint32
                           : "Ward: alpha >= 0.05 (both components) and a sampling weight in [0, 1]");
       if (!bsdfWardVariantValid(b)) return fail(h, GVPM_ERR_UNSUPPORTED, "Ward: variant ward / ward-duer / balanced, both components");
     } else if (!bsdfMicrofacetValid(b)) {
-      return fail(h, GVPM_ERR_UNSUPPORTED, "rough conductor: Beckmann or GGX");
+      return fail(h, GVPM_ERR_UNSUPPORTED, "rough conductor: Beckmann, GGX or Phong / Ashikhmin-Shirley");
+    } else if (!bsdfSampleVisibleValid(b)) {
+      return fail(h, GVPM_ERR_INVALID_ARG, "rough conductor: the Phong / Ashikhmin-Shirley distribution samples all normals (sample_visible = 0)");
     }
   } else if (b.kind == GVPM_BSDF_ROUGHPLASTIC || b.kind == GVPM_BSDF_PLASTIC) {
     // (include/gvpm_hip.h: eta[0] = eta, eta[1] = Fdr, k[0] = the component met, k[1] = nonlinear)
     const bool rough = b.kind == GVPM_BSDF_ROUGHPLASTIC;
     if (rough && !bsdfAlphaValid(b.exponent)) return fail(h, GVPM_ERR_INVALID_ARG, "rough plastic: alpha >= 1e-4 (the reference clamps it)");
-    if (rough && !bsdfMicrofacetValid(b)) return fail(h, GVPM_ERR_UNSUPPORTED, "rough plastic: Beckmann or GGX");
+    if (rough && !bsdfMicrofacetValid(b)) return fail(h, GVPM_ERR_UNSUPPORTED, "rough plastic: Beckmann, GGX or Phong");
+    if (rough && !bsdfSampleVisibleValid(b)) return fail(h, GVPM_ERR_INVALID_ARG, "rough plastic: the Phong / Ashikhmin-Shirley distribution samples all normals (sample_visible = 0)");
     if (!(b.eta[0] >= 1.f && b.eta[0] <= FLT_MAX) || !(b.eta[1] >= 0.f && b.eta[1] < 1.f) || !weightOk)
       return fail(h, GVPM_ERR_INVALID_ARG, "plastic: eta >= 1 and finite, Fdr in [0, 1), a sampling weight in [0, 1]");
     if (rough ? !(b.k[0] == 0.f || b.k[0] == 1.f || b.k[0] == 2.f) : b.k[0] != 2.f)
@@ -445,7 +448,8 @@ static int checkBsdf(gvpm_context *h, const gvpm_bsdf *table, uint32_t i, uint32
         return fail(h, GVPM_ERR_INVALID_ARG, "rough dielectric: reflectance and transmittance channels in [0, 1]");
     if (!bsdfDielectricZerosValid(b))
       return fail(h, GVPM_ERR_INVALID_ARG, "rough dielectric: eta[1], eta[2], the sampling weight and the reserved words are zero");
-    if (!bsdfMicrofacetValid(b)) return fail(h, GVPM_ERR_UNSUPPORTED, "rough dielectric: Beckmann or GGX");
+    if (!bsdfMicrofacetValid(b)) return fail(h, GVPM_ERR_UNSUPPORTED, "rough dielectric: Beckmann, GGX or Phong");
+    if (!bsdfSampleVisibleValid(b)) return fail(h, GVPM_ERR_INVALID_ARG, "rough dielectric: the Phong / Ashikhmin-Shirley distribution samples all normals (sample_visible = 0)");
   } else {
     return fail(h, GVPM_ERR_UNSUPPORTED,
                 "bsdf kind outside the device's closed set (Phong, rough conductor, Ward, the plastics, anisotropic Ward / rough conductor, "

@@ -16,25 +16,31 @@ namespace gvpm {
 
 // MicrofacetDistribution, isotropic (src/bsdfs/microfacet.h): D of a half vector with cosine cH to the normal (:191-232) and
 // Smith's G1 of a direction with cosine cV to the normal and vDotH to the half vector (:477-518).
-__device__ __forceinline__ float microfacetD(int ggx, float alpha, float cH) {
+// The Phong / Ashikhmin-Shirley distribution (GVPM_MICROFACET_PHONG) has the exponent max(2 / alpha^2 - 2, 0) (:700-704) and
+// D = (e + 2) / (2 pi) cos^e; the power is formed as the Phong kind forms its lobe.  Its G1 is Beckmann's, with alpha (:489-501).
+__device__ __forceinline__ float phongExponent(float alpha) { return fmaxf(fdiv(2.f, alpha * alpha) - 2.f, 0.f); }
+__device__ __forceinline__ float microfacetD(int dist, float alpha, float cH) {
   if (cH <= 0.f) return 0.f;
   const float c2 = cH * cH;
-  const float e = fdiv(fmaxf(1.f - c2, 0.f), alpha * alpha * c2);  // tan^2 / alpha^2
+  const float e = fdiv(fmaxf(1.f - c2, 0.f), alpha * alpha * c2);  // tan^2 / alpha^2: Beckmann's and GGX's; the Phong arm does not read it
   float r;
-  if (ggx) {
+  if (dist == GVPM_MICROFACET_GGX) {
     const float root = (1.f + e) * c2;
     r = frcp(PI_F * alpha * alpha * root * root);
-  } else {
+  } else if (dist != GVPM_MICROFACET_PHONG) {
     r = fdiv(__expf(-e), PI_F * alpha * alpha * c2 * c2);
+  } else {
+    const float ex = phongExponent(alpha);  // (the Phong EXPONENT, not `e` above)
+    r = (ex + 2.f) * INV_TWOPI_F * __builtin_exp2f(ex * __builtin_log2f(cH));  // std::pow(cos(theta_m), exponent)
   }
   return r * cH < 1e-20f ? 0.f : r;
 }
-__device__ __forceinline__ float microfacetG1(int ggx, float alpha, float cV, float vDotH) {
+__device__ __forceinline__ float microfacetG1(int dist, float alpha, float cV, float vDotH) {
   if (vDotH * cV <= 0.f) return 0.f;
   const float t2 = 1.f - cV * cV;
   if (t2 <= 0.f) return 1.f;  // perpendicular incidence
   const float tanT = fabsf(fdiv(fsqrt(t2), cV));
-  if (ggx) {
+  if (dist == GVPM_MICROFACET_GGX) {
     const float root = alpha * tanT;
     return fdiv(2.f, 1.f + fsqrt(1.f + root * root));
   }
@@ -57,16 +63,23 @@ __device__ __forceinline__ bool anisoFrame(const float4 fr, f3 n, f3 &s, f3 &t) 
   return true;
 }
 // MicrofacetDistribution::eval with alphaU != alphaV (microfacet.h:191-232): mx, my, cH = the unit half vector in the frame
-__device__ __forceinline__ float microfacetDAniso(int ggx, float au, float av, float mx, float my, float cH) {
+// Ashikhmin-Shirley (GVPM_MICROFACET_PHONG): the exponent interpolated between eU and eV by the half vector's azimuth
+// (interpolatePhongExponent, :553-565: eU where alphaU == alphaV or sin^2(theta_m) <= RCPOVERFLOW), D = sqrt((eU + 2)(eV + 2)) /
+// (2 pi) cos^e
+__device__ __forceinline__ float microfacetDAniso(int dist, float au, float av, float mx, float my, float cH) {
   if (cH <= 0.f) return 0.f;
   const float c2 = cH * cH, ux = fdiv(mx, au), uy = fdiv(my, av);
-  const float e = fdiv(ux * ux + uy * uy, c2);
+  const float e = fdiv(ux * ux + uy * uy, c2);  // (Beckmann's and GGX's; the Phong arm reads neither it nor ux, uy)
   float r;
-  if (ggx) {
+  if (dist == GVPM_MICROFACET_GGX) {
     const float root = (1.f + e) * c2;
     r = frcp(PI_F * au * av * root * root);
-  } else {
+  } else if (dist != GVPM_MICROFACET_PHONG) {
     r = fdiv(__expf(-e), PI_F * au * av * c2 * c2);
+  } else {
+    const float eU = phongExponent(au), eV = phongExponent(av), s2 = 1.f - c2;
+    const float ex = (au == av || s2 <= 0x1p-128f) ? eU : fdiv(eU * (mx * mx) + eV * (my * my), s2);
+    r = fsqrt((eU + 2.f) * (eV + 2.f)) * INV_TWOPI_F * __builtin_exp2f(ex * __builtin_log2f(cH));
   }
   return r * cH < 1e-20f ? 0.f : r;
 }
@@ -134,7 +147,7 @@ __device__ __forceinline__ float4 roughDielectricEval(const float4 *__restrict__
   const float sgn = cosWi > 0.f ? 1.f : -1.f, ci = fabsf(cosWi), co = cosWo * sgn;
   const bool reflect = cosWi > 0.f;
   const float eta = bsdfDielectricEta(b2), alpha = bsdfAlpha(b1);
-  const int ggx = bsdfDistribution(b1) == GVPM_MICROFACET_GGX, vis = bsdfSampleVisible(b1) != 0;
+  const int dist = bsdfDistribution(b1), vis = bsdfSampleVisible(b1) != 0;
   f3 H = reflect ? wi + wo : wi + wo * eta;
   const float HH = dot(H, H);
   if (HH < 1e-12f) return make_float4(0.f, 0.f, 0.f, -1.f);
@@ -149,11 +162,11 @@ __device__ __forceinline__ float4 roughDielectricEval(const float4 *__restrict__
   // trick scaled (:406-414) with its own `D' cos_H < 1e-20` cut.  D == 0 gives eval = 0 (:315-316) -- and pdf = 0 only if D' is
   // zero too: RoughDielectric::pdf does not look at D, so a half vector in the band between the two cuts is a shift that
   // SUCCEEDS with zero flux (the products below are 0 x finite)
-  const float D = microfacetD(ggx, alpha, cH);
-  const float Ds = vis ? D : microfacetD(ggx, alpha * (1.2f - 0.2f * fsqrt(ci)), cH);
+  const float D = microfacetD(dist, alpha, cH);
+  const float Ds = vis ? D : microfacetD(dist, alpha * (1.2f - 0.2f * fsqrt(ci)), cH);
   if (D == 0.f && Ds == 0.f) return make_float4(0.f, 0.f, 0.f, 0.f);
   const float F = fresnelDielectricExt(wiH, eta);
-  const float G1i = microfacetG1(ggx, alpha, ci, wiH), G1o = microfacetG1(ggx, alpha, co, woH);
+  const float G1i = microfacetG1(dist, alpha, ci, wiH), G1o = microfacetG1(dist, alpha, co, woH);
   f3 f;
   float dwh;
   if (reflect) {
@@ -251,25 +264,25 @@ __device__ __forceinline__ bool glossyParentEval(const GatherArgs &a, float inde
   if (kind == GVPM_BSDF_ROUGHCONDUCTOR || kind == GVPM_BSDF_ROUGHCONDUCTOR_ANISO) {
     const float4 b2 = a.bsdfs[4 * bi + 2], b3 = a.bsdfs[4 * bi + 3];
     const float alpha = bsdfAlpha(b1);
-    const int ggx = bsdfDistribution(b1) == GVPM_MICROFACET_GGX, vis = bsdfSampleVisible(b1) != 0;
+    const int dist = bsdfDistribution(b1), vis = bsdfSampleVisible(b1) != 0;
     f3 H = wi + wo;
     H = H * frsq(dot(H, H));
     const float cH = dot(H, n), wiH = dot(wi, H), woH = dot(wo, H);
     float D, alI = alpha, alO = alpha;  // (anisotropic: alphaU = the head's alpha, the roughness projected on wi and on wo)
     if (kind == GVPM_BSDF_ROUGHCONDUCTOR) {
-      D = microfacetD(ggx, alpha, cH);
+      D = microfacetD(dist, alpha, cH);
     } else {
       const float4 fr = a.bsdfs[4 * (bi + 1)];
       f3 s, t;
       if (!anisoFrame(fr, n, s, t)) return false;
-      D = microfacetDAniso(ggx, alpha, bsdfFrameAlphaV(fr), dot(H, s), dot(H, t), cH);
+      D = microfacetDAniso(dist, alpha, bsdfFrameAlphaV(fr), dot(H, s), dot(H, t), cH);
       if (D != 0.f) {
         alI = projectRoughness(alpha, bsdfFrameAlphaV(fr), dot(wi, s), dot(wi, t), cosWi);
         alO = projectRoughness(alpha, bsdfFrameAlphaV(fr), dot(wo, s), dot(wo, t), cosWo);
       }
     }
     if (D == 0.f) return true;  // eval and pdf both zero (pdfAll = D cos_H, pdfVisible = D G1 ...)
-    const float G1i = microfacetG1(ggx, alI, cosWi, wiH), G1o = microfacetG1(ggx, alO, cosWo, woH);
+    const float G1i = microfacetG1(dist, alI, cosWi, wiH), G1o = microfacetG1(dist, alO, cosWo, woH);
     const float model = fdiv(D * G1i * G1o, 4.f * cosWi);
     f = mk3(fresnelConductor(wiH, bsdfConductorEta<0>(b2), bsdfConductorK<0>(b2, b3)) * bsdfSpecular<0>(b0),
             fresnelConductor(wiH, bsdfConductorEta<1>(b2), bsdfConductorK<1>(b2, b3)) * bsdfSpecular<1>(b0),
@@ -290,13 +303,13 @@ __device__ __forceinline__ bool glossyParentEval(const GatherArgs &a, float inde
       Ti = roughTransmittance(slice, cosWi);
       To = roughTransmittance(slice, cosWo);
       const float alpha = bsdfAlpha(b1);
-      const int ggx = bsdfDistribution(b1) == GVPM_MICROFACET_GGX, vis = bsdfSampleVisible(b1) != 0;
+      const int dist = bsdfDistribution(b1), vis = bsdfSampleVisible(b1) != 0;
       f3 H = wi + wo;
       H = H * frsq(dot(H, H));
       const float cH = dot(H, n), wiH = dot(wi, H), woH = dot(wo, H);
-      const float D = microfacetD(ggx, alpha, cH);
+      const float D = microfacetD(dist, alpha, cH);
       if (D != 0.f && comp != 2) {
-        const float G1i = microfacetG1(ggx, alpha, cosWi, wiH), G1o = microfacetG1(ggx, alpha, cosWo, woH);
+        const float G1i = microfacetG1(dist, alpha, cosWi, wiH), G1o = microfacetG1(dist, alpha, cosWo, woH);
         spec = fresnelDielectric(wiH, eta) * fdiv(D * G1i * G1o, 4.f * cosWi);
         pdfM = vis ? fdiv(D * G1i, 4.f * cosWi) : fdiv(D * cH, 4.f * fabsf(woH));
       }

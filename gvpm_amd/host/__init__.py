@@ -52,6 +52,7 @@ def lib():
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
         L.gvpm_synth_sample_aniso.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
+        L.gvpm_synth_sample_conductor.argtypes = L.gvpm_synth_sample_aniso.argtypes
         L.gvpm_synth_sample_dielectric.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gvpm_synth_sensor.argtypes = [C.c_void_p, C.POINTER(abi.Sensor)]
@@ -104,15 +105,15 @@ class SynthScene:
         return out
 
     def rtrans_materials(self):
-        """the scene's rough-plastic materials, in table order: [(material index, "beckmann" | "ggx", alpha, eta)] -- each needs
+        """the scene's rough-plastic materials, in table order: [(material index, "beckmann" | "ggx" | "phong", alpha, eta)] -- each needs
         its transmittance slice (set_rtrans) before photons or beams are shot"""
         n = lib().gvpm_synth_rtrans_materials(self._h, None, None, None, None, 0)
         mats, dist = np.zeros(n, np.int32), np.zeros(n, np.int32)
         alpha, eta = np.zeros(n, np.float32), np.zeros(n, np.float32)
         if n:
             lib().gvpm_synth_rtrans_materials(self._h, mats.ctypes.data, dist.ctypes.data, alpha.ctypes.data, eta.ctypes.data, n)
-        return [(int(mats[i]), "ggx" if dist[i] == abi.GVPM_MICROFACET_GGX else "beckmann", float(alpha[i]), float(eta[i]))
-                for i in range(n)]
+        names = {abi.GVPM_MICROFACET_BECKMANN: "beckmann", abi.GVPM_MICROFACET_GGX: "ggx", abi.GVPM_MICROFACET_PHONG: "phong"}
+        return [(int(mats[i]), names[int(dist[i])], float(alpha[i]), float(eta[i])) for i in range(n)]
 
     def set_rtrans(self, mat, values, fdr):
         """the rough transmittance of material `mat` at its eta and alpha: 100 values in [0, 1] over cos^(1/4) (the slice the
@@ -134,6 +135,18 @@ class SynthScene:
         if rc < 0:
             raise ValueError(f"sample_plastic({mat}): not a plastic material, or its slice is missing")
         return (wo, weight, pdf.value, comp.value) if rc == 1 else None
+
+    def sample_conductor(self, mat, n, wi, u1, u2):
+        """one bounce off isotropic rough-conductor material `mat` as the light-path walk takes it: (wo, weight, pdf) or None when
+        the sample is lost"""
+        n, wi = np.ascontiguousarray(n, np.float64), np.ascontiguousarray(wi, np.float64)
+        wo, weight = np.zeros(3), np.zeros(3)
+        pdf = C.c_double(0)
+        rc = lib().gvpm_synth_sample_conductor(self._h, mat, n.ctypes.data, wi.ctypes.data, u1, u2, wo.ctypes.data, weight.ctypes.data,
+                                               C.addressof(pdf))
+        if rc < 0:
+            raise ValueError(f"sample_conductor({mat}): not an isotropic rough conductor")
+        return (wo, weight, pdf.value) if rc == 1 else None
 
     def sample_aniso(self, mat, n, wi, u1, u2):
         """one bounce off anisotropic Ward / rough-conductor material `mat` as the light-path walk takes it (the material's own

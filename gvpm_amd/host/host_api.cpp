@@ -179,6 +179,20 @@ int gvpm_synth_sample_plastic(const gvpm_synth *s, int mat, const double *n, con
   return 1;
 }
 
+int gvpm_synth_sample_conductor(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
+                                double *weight, double *pdf) {
+  using namespace gvpm;
+  if (!s || !n || !wi || !wo || !weight || !pdf || mat < 0 || mat >= (int)s->scene.mats.size()) return GVPM_ERR_INVALID_ARG;
+  const SynthMat &pm = s->scene.mats[mat];
+  if (pm.kind != MAT_ROUGHCONDUCTOR) return GVPM_ERR_INVALID_ARG;
+  V3 o, w;
+  uint32_t comp = 0;
+  if (!sampleConductor(pm, V3(n[0], n[1], n[2]), V3(wi[0], wi[1], wi[2]), u1, u2, o, w, *pdf, comp)) return 0;
+  wo[0] = o.x; wo[1] = o.y; wo[2] = o.z;
+  weight[0] = w.x; weight[1] = w.y; weight[2] = w.z;
+  return 1;
+}
+
 int gvpm_synth_sample_aniso(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
                             double *weight, double *pdf) {
   using namespace gvpm;

@@ -44,6 +44,11 @@ int gvpm_synth_set_rtrans(gvpm_synth *s, int mat, const float *values, int n, fl
  * 0 when the sample is lost, GVPM_ERR_INVALID_ARG for another kind of material or a missing slice. */
 int gvpm_synth_sample_plastic(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
                               double *weight, double *pdf, int *component);
+/* A TEST HOOK like gvpm_synth_sample_plastic, for the isotropic rough-conductor materials (scenes cbox_conductor,
+ * cbox_conductor_phong; synth_core.h sampleConductor).  Returns 1 and wo, weight (eval / pdf), pdf (solid angle), 0 when the
+ * sample is lost, GVPM_ERR_INVALID_ARG for another kind of material. */
+int gvpm_synth_sample_conductor(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
+                                double *weight, double *pdf);
 /* A TEST HOOK like gvpm_synth_sample_plastic, for the anisotropic Ward / rough-conductor materials (scenes cbox_ward_aniso,
  * cbox_conductor_aniso; synth_core.h sampleAniso): one bounce with the material's own tangent and alphas.  Returns 1 and wo,
  * weight (eval / pdf), pdf (solid angle), 0 when the sample is lost (a tangent parallel to n among the reasons),

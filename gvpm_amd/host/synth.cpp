@@ -244,6 +244,31 @@ bool makeScene(const std::string &fullName, int width, int height, uint32_t seed
     if (rot) addCornellBlocks(s, 0, mBack);
     setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);
     setMedium(s, 0.5, 0.5, 0.0);
+  } else if (name == "cbox_conductor_phong") {
+    // cbox_conductor's walls under the PHONG microfacet distribution (microfacet.h, EPhong): the copper floor isotropic, alpha
+    // 0.3 (exponent 20.2); the aluminium back wall Ashikhmin-Shirley, 0.35 x 0.08 (exponents 14.3 and 310.5), brushed along the
+    // tangent cbox_conductor_aniso gives its back wall
+    auto conductor = [&](int kind, V3 eta, V3 k, double alphaU, double alphaV, V3 tangent) {
+      SynthMat m{kind, V3(0.0), V3(1.0), alphaU, 0.0, 0};
+      m.eta = eta;
+      m.k = k;
+      m.distribution = GVPM_MICROFACET_PHONG;
+      if (kind == MAT_ROUGHCONDUCTOR_ANISO) {
+        m.alphaV = alphaV;
+        m.tangent = s.toWorld(normalize(tangent));
+      }
+      m.bsdf = 0;
+      for (const auto &q : s.mats) m.bsdf += bsdfSlots(q.kind, q.exponent);
+      s.mats.push_back(m);
+      return (int)s.mats.size() - 1;
+    };
+    const int mFloor = conductor(MAT_ROUGHCONDUCTOR, V3(0.2004, 0.9240, 1.1022), V3(3.9129, 2.4528, 2.1421), 0.3, 0.3, V3(0.0));
+    const int mBack = conductor(MAT_ROUGHCONDUCTOR_ANISO, V3(1.6574, 0.8803, 0.5212), V3(9.2238, 6.2695, 4.8370), 0.35, 0.08,
+                                V3(0.9, 0.35, 0.25));
+    addBoxRoom(s, mFloor, 0, mBack, 1, 2, 3);
+    if (rot) addCornellBlocks(s, 0, 0);  // (white blocks: an anisotropic material sits on ONE plane)
+    setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);
+    setMedium(s, 0.5, 0.5, 0.0);
   } else if (name == "cbox_ward_aniso" || name == "cbox_conductor_aniso") {
     // S-cbox with ANISOTROPIC walls (row f4): brushed surfaces, alphaU != alphaV, the brushing direction a per-material
     // world-space tangent (the walls are planar; the `_rot` scenes turn it with everything else).  cbox_ward_aniso: the floor a
@@ -278,11 +303,14 @@ bool makeScene(const std::string &fullName, int width, int height, uint32_t seed
     if (rot) addCornellBlocks(s, 0, 0);  // (white blocks: an anisotropic material sits on ONE plane, it has one tangent)
     setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);
     setMedium(s, 0.5, 0.5, 0.0);
-  } else if (name == "cbox_roughplastic" || name == "cbox_roughplastic1" || name == "cbox_plastic") {
+  } else if (name == "cbox_roughplastic" || name == "cbox_roughplastic1" || name == "cbox_roughplastic_phong" || name == "cbox_plastic") {
     // S-cbox with PLASTIC walls (row f4): floor and back wall a dielectric coating (eta 1.5) over a diffuse base --
     // src/bsdfs/roughplastic.cpp (floor Beckmann alpha 0.1, back wall GGX alpha 0.3; `1`: 0.03 / 0.04, below 0.05, so one
     // component per bounce) or src/bsdfs/plastic.cpp (smooth).  The rough kinds need their transmittance slice before the
     // first walk (SynthScene::setRtrans); Fdr comes with it, the smooth plastic's m_fdrInt is closed-form.
+    // `cbox_roughplastic_phong`: alpha 0.1 and 0.3 under the Phong distribution, both components.
+    const int distFloor = name == "cbox_roughplastic_phong" ? GVPM_MICROFACET_PHONG : GVPM_MICROFACET_BECKMANN;
+    const int distBack = name == "cbox_roughplastic_phong" ? GVPM_MICROFACET_PHONG : GVPM_MICROFACET_GGX;
     const bool smooth = name == "cbox_plastic", one = name == "cbox_roughplastic1";
     auto plastic = [&](V3 kd, V3 ks, double alpha, int distribution, bool nonlinear) {
       auto lum = [](V3 c) { return 0.212671 * c.x + 0.715160 * c.y + 0.072169 * c.z; };  // Spectrum::getLuminance, RGB
@@ -312,24 +340,25 @@ bool makeScene(const std::string &fullName, int width, int height, uint32_t seed
     };
     // (a coated surface is darker than its base: kd' T T / eta^2 is about 0.36 kd / (1 - 0.6 [kd]); bright bases keep as many
     // photons behind these walls as behind the Phong ones)
-    const int mFloor = plastic(V3(0.7, 0.7, 0.7), V3(1.0, 1.0, 0.9), one ? 0.03 : 0.1, GVPM_MICROFACET_BECKMANN, false);
-    const int mBack = plastic(V3(0.6, 0.7, 0.9), V3(0.9, 0.9, 0.9), one ? 0.04 : 0.3, GVPM_MICROFACET_GGX, true);
+    const int mFloor = plastic(V3(0.7, 0.7, 0.7), V3(1.0, 1.0, 0.9), one ? 0.03 : 0.1, distFloor, false);
+    const int mBack = plastic(V3(0.6, 0.7, 0.9), V3(0.9, 0.9, 0.9), one ? 0.04 : 0.3, distBack, true);
     addBoxRoom(s, mFloor, 0, mBack, 1, 2, 3);
     if (rot) addCornellBlocks(s, 0, mBack);
     setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);
     setMedium(s, 0.5, 0.5, 0.0);
-  } else if (name == "cbox_roughglass" || name == "cbox_roughglass_ggx") {
+  } else if (name == "cbox_roughglass" || name == "cbox_roughglass_ggx" || name == "cbox_roughglass_phong") {
     // S-cbox with Lambertian walls and a ROUGH-GLASS pane across the whole room under the light (row f4; src/bsdfs/
     // roughdielectric.cpp -- a material of the bathroom scene BASELINE configs[3] is named after): eta 1.5, Beckmann alpha 0.25, its
     // front (the side eta belongs to) up.  Everything below the pane is lit through it: photons behind it were transmitted,
     // photons above it reflected, and light that comes back from the room meets it from inside.  Reflectance and transmittance
     // are tinted differently, so that a swapped pair shows.  `_rot`: the pane is tilted in the room as well, its plane in
     // general position there -- a parent's fp32 position falls either side of it.  `cbox_roughglass_ggx`: the same pane with
-    // the GGX distribution.
+    // the GGX distribution, `cbox_roughglass_phong`: with the Phong one.
     SynthMat m{MAT_ROUGHDIELECTRIC, V3(0.0), V3(1.0, 0.95, 0.9), 0.25, 0.0, 0};
     m.coatEta = 1.5;
     m.k = V3(0.9, 0.95, 1.0);
-    m.distribution = name == "cbox_roughglass_ggx" ? GVPM_MICROFACET_GGX : GVPM_MICROFACET_BECKMANN;
+    m.distribution = name == "cbox_roughglass_ggx" ? GVPM_MICROFACET_GGX
+                     : name == "cbox_roughglass_phong" ? GVPM_MICROFACET_PHONG : GVPM_MICROFACET_BECKMANN;
     m.bsdf = 0;
     for (const auto &q : s.mats) m.bsdf += bsdfSlots(q.kind, q.exponent);
     s.mats.push_back(m);

@@ -126,24 +126,30 @@ constexpr double kInvFourPi = 1.0 / (4.0 * kPi);
 constexpr double kEpsilon = 1e-4;  // Epsilon, single-precision build (constants.h:24-31)
 
 // isotropic microfacet terms of the rough conductor (microfacet.h:191-232, 477-518; util.cpp:747-769), by cosines
-GVPM_HD inline double conductorD(int ggx, double alpha, double cH) {
+// (`dist` = GVPM_MICROFACET_*.  The Phong / Ashikhmin-Shirley distribution: exponent max(2 / alpha^2 - 2, 0), :700-704;
+// D = (e + 2) / (2 pi) cos^e; G1 is Beckmann's with alpha, :489-501)
+GVPM_HD inline double phongDistExponent(double alpha) { return std::fmax(2.0 / (alpha * alpha) - 2.0, 0.0); }
+GVPM_HD inline double conductorD(int dist, double alpha, double cH) {
   if (cH <= 0) return 0;
   const double c2 = cH * cH, e = (1 - c2) / (alpha * alpha * c2);
   double r;
-  if (ggx) {
+  if (dist == GVPM_MICROFACET_GGX) {
     const double root = (1 + e) * c2;
     r = 1.0 / (kPi * alpha * alpha * root * root);
+  } else if (dist == GVPM_MICROFACET_PHONG) {
+    const double ex = phongDistExponent(alpha);
+    r = (ex + 2) / (2.0 * kPi) * std::pow(cH, ex);
   } else {
     r = std::exp(-e) / (kPi * alpha * alpha * c2 * c2);
   }
   return r * cH < 1e-20 ? 0.0 : r;
 }
-GVPM_HD inline double conductorG1(int ggx, double alpha, double cV, double vDotH) {
+GVPM_HD inline double conductorG1(int dist, double alpha, double cV, double vDotH) {
   if (vDotH * cV <= 0) return 0;
   const double t2 = 1 - cV * cV;
   if (t2 <= 0) return 1;
   const double tanT = std::fabs(std::sqrt(t2) / cV);
-  if (ggx) {
+  if (dist == GVPM_MICROFACET_GGX) {
     const double root = alpha * tanT;
     return 2.0 / (1.0 + std::sqrt(1.0 + root * root));
   }
@@ -163,13 +169,18 @@ GVPM_HD inline double conductorFresnel(double cI, double eta, double k) {
 }
 // the same two terms with alphaU != alphaV (microfacet.h:191-232, :477-518 over projectRoughness, :541-551): (mx, my, cH) the
 // unit half vector in the shading frame, (vx, vy, cV) a unit direction in it
-GVPM_HD inline double conductorDAniso(int ggx, double au, double av, double mx, double my, double cH) {
+GVPM_HD inline double conductorDAniso(int dist, double au, double av, double mx, double my, double cH) {
   if (cH <= 0) return 0;
   const double c2 = cH * cH, e = (mx * mx / (au * au) + my * my / (av * av)) / c2;
   double r;
-  if (ggx) {
+  if (dist == GVPM_MICROFACET_GGX) {
     const double root = (1 + e) * c2;
     r = 1.0 / (kPi * au * av * root * root);
+  } else if (dist == GVPM_MICROFACET_PHONG) {
+    // interpolatePhongExponent (:553-565): eU where alphaU == alphaV or sin^2(theta_m) <= RCPOVERFLOW (constants.h:58)
+    const double eU = phongDistExponent(au), eV = phongDistExponent(av), s2 = 1 - c2;
+    const double ex = (au == av || s2 <= 0x1p-128) ? eU : (eU * mx * mx + eV * my * my) / s2;
+    r = std::sqrt((eU + 2) * (eV + 2)) / (2.0 * kPi) * std::pow(cH, ex);
   } else {
     r = std::exp(-e) / (kPi * au * av * c2 * c2);
   }
@@ -319,6 +330,67 @@ GVPM_HD inline double hgEval(double g, double cosWiWo) {
 }
 
 #if GVPM_SYNTH_GLOSSY
+// MicrofacetDistribution::sampleAll for the Phong / Ashikhmin-Shirley distribution (microfacet.h:349-375): (a, b) = (sample.x,
+// sample.y).  Isotropic: phi = 2 pi b and the exponent eU; else the azimuth of the first quadrant (sampleFirstQuadrant, :707-715)
+// mirrored into b's quadrant, with the exponent interpolated at it.  cos(theta_m) = a^(1 / (e + 2)), pdf = sqrt((eU + 2)(eV + 2))
+// / (2 pi) cos^(e + 1); the caller applies the `pdf < 1e-20` cut.
+inline void samplePhongDist(double au, double av, double a, double b, double &cosThetaM, double &phiM, double &pdfM) {
+  const double eU = phongDistExponent(au), eV = phongDistExponent(av);
+  double ex = eU;
+  if (au == av) {
+    phiM = 2.0 * kPi * b;
+  } else {
+    auto quadrant = [&](double u1) {
+      const double phi = std::atan(std::sqrt((eU + 2.0) / (eV + 2.0)) * std::tan(kPi * u1 * 0.5));
+      const double c = std::cos(phi), sn = std::sin(phi);
+      ex = eU * c * c + eV * sn * sn;
+      return phi;
+    };
+    if (b < 0.25) phiM = quadrant(4 * b);
+    else if (b < 0.5) phiM = kPi - quadrant(4 * (0.5 - b));
+    else if (b < 0.75) phiM = quadrant(4 * (b - 0.5)) + kPi;
+    else phiM = 2 * kPi - quadrant(4 * (1 - b));
+  }
+  cosThetaM = std::pow(a, 1.0 / (ex + 2.0));
+  pdfM = std::sqrt((eU + 2.0) * (eV + 2.0)) / (2.0 * kPi) * std::pow(cosThetaM, ex + 1.0);
+}
+
+// One bounce off an isotropic rough conductor: RoughConductor::sample, sampleVisible = false (roughconductor.cpp:321-389 with
+// MicrofacetDistribution::sampleAll, microfacet.h:287-375): half vector m ~ D cos, wo = reflect(wi, m), weight = F D G (wi . m) /
+// (pdf_m cos_i), pdf = pdf_m / (4 |wo . m|).  (a, b) = (sample.x, sample.y).  False: the sample is lost.
+inline bool sampleConductor(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
+  const double alpha = pm.exponent, alphaSqr = alpha * alpha, cosWi = dot(n, wi);
+  double tanThetaMSqr, pdfM, cosThetaM, phi = 2.0 * kPi * b;
+  if (pm.distribution == GVPM_MICROFACET_PHONG) {
+    samplePhongDist(alpha, alpha, a, b, cosThetaM, phi, pdfM);
+  } else if (pm.distribution == GVPM_MICROFACET_GGX) {
+    tanThetaMSqr = alphaSqr * a / (1.0 - a);
+    cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
+    const double temp = 1 + tanThetaMSqr / alphaSqr;
+    pdfM = kInvPi / (alphaSqr * cosThetaM * cosThetaM * cosThetaM * temp * temp);
+  } else {
+    tanThetaMSqr = alphaSqr * -std::log(1.0 - a);
+    cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
+    pdfM = (1.0 - a) / (kPi * alphaSqr * cosThetaM * cosThetaM * cosThetaM);
+  }
+  if (!(pdfM >= 1e-20)) return false;
+  const double sinThetaM = std::sqrt(std::fmax(0.0, 1 - cosThetaM * cosThetaM));
+  const V3 m = toWorld(n, V3(sinThetaM * std::cos(phi), sinThetaM * std::sin(phi), cosThetaM));
+  const double wiM = dot(wi, m);
+  wo = m * (2.0 * wiM) - wi;
+  const double cosWo = dot(n, wo);
+  if (cosWo <= 0) return false;
+  const double woM = dot(wo, m);
+  const double D = conductorD(pm.distribution, alpha, cosThetaM);
+  const double G = conductorG1(pm.distribution, alpha, cosWi, wiM) * conductorG1(pm.distribution, alpha, cosWo, woM);
+  const double wgt = D * G * wiM / (pdfM * cosWi);
+  weight = V3(conductorFresnel(wiM, pm.eta.x, pm.k.x) * pm.spec.x, conductorFresnel(wiM, pm.eta.y, pm.k.y) * pm.spec.y,
+              conductorFresnel(wiM, pm.eta.z, pm.k.z) * pm.spec.z) * wgt;
+  pdf = pdfM / (4.0 * std::fabs(woM));
+  comp = 0x00008u;  // EGlossyReflection
+  return maxc(weight) > 0 && pdf > 0;
+}
+
 // One bounce off an anisotropic Ward / rough-conductor surface.  The shading frame is (s', t, n) with s' the material's tangent
 // projected into the surface and t = n x s' (what the device rebuilds from the table's frame entry).  (a, b) = (sample.x,
 // sample.y).  Ward::sample with bRec.component = -1 (ward.cpp:268-327; roughness 0.5 (alphaU + alphaV) >= 0.05): phiH / thetaH
@@ -376,17 +448,18 @@ inline bool sampleAniso(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 
     return maxc(weight) > 0;
   }
   // the rough conductor
-  const int ggx = pm.distribution == GVPM_MICROFACET_GGX;
-  const double phiM = std::atan(av / au * std::tan(kPi + 2 * kPi * b)) + kPi * std::floor(2 * b + 0.5);
+  const int dist = pm.distribution;
+  double phiM = std::atan(av / au * std::tan(kPi + 2 * kPi * b)) + kPi * std::floor(2 * b + 0.5);
+  double tanThetaMSqr, pdfM, cosThetaM;
+  if (dist == GVPM_MICROFACET_PHONG) samplePhongDist(au, av, a, b, cosThetaM, phiM, pdfM);  // (with its own azimuth)
   const double sinPhiM = std::sin(phiM), cosPhiM = std::cos(phiM);
   const double cosSc = cosPhiM / au, sinSc = sinPhiM / av, alphaSqr = 1.0 / (cosSc * cosSc + sinSc * sinSc);
-  double tanThetaMSqr, pdfM, cosThetaM;
-  if (ggx) {
+  if (dist == GVPM_MICROFACET_GGX) {
     tanThetaMSqr = alphaSqr * a / (1.0 - a);
     cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
     const double temp = 1 + tanThetaMSqr / alphaSqr;
     pdfM = kInvPi / (au * av * cosThetaM * cosThetaM * cosThetaM * temp * temp);
-  } else {
+  } else if (dist != GVPM_MICROFACET_PHONG) {
     tanThetaMSqr = alphaSqr * -std::log(1.0 - a);
     cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
     pdfM = (1.0 - a) / (kPi * au * av * cosThetaM * cosThetaM * cosThetaM);
@@ -400,9 +473,9 @@ inline bool sampleAniso(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 
   const double cosWo = dot(n, wo);
   if (cosWo <= 0) return false;
   const double woM = dot(wo, m);
-  const double D = conductorDAniso(ggx, au, av, mx, my, cosThetaM);
-  const double G = conductorG1(ggx, projectedAlpha(au, av, dot(wi, sp), dot(wi, tp), cosWi), cosWi, wiM) *
-                   conductorG1(ggx, projectedAlpha(au, av, dot(wo, sp), dot(wo, tp), cosWo), cosWo, woM);
+  const double D = conductorDAniso(dist, au, av, mx, my, cosThetaM);
+  const double G = conductorG1(dist, projectedAlpha(au, av, dot(wi, sp), dot(wi, tp), cosWi), cosWi, wiM) *
+                   conductorG1(dist, projectedAlpha(au, av, dot(wo, sp), dot(wo, tp), cosWo), cosWo, woM);
   const double wgt = D * G * wiM / (pdfM * cosWi);
   weight = V3(conductorFresnel(wiM, pm.eta.x, pm.k.x) * pm.spec.x, conductorFresnel(wiM, pm.eta.y, pm.k.y) * pm.spec.y,
               conductorFresnel(wiM, pm.eta.z, pm.k.z) * pm.spec.z) * wgt;
@@ -440,10 +513,12 @@ inline bool sampleDielectric(const SynthMat &pm, V3 n, V3 wi, double a, double b
   if (cosN == 0) return false;
   const V3 nI = cosN > 0 ? n : -n;
   const double ci = std::fabs(cosN), eta = cosN > 0 ? pm.coatEta : 1.0 / pm.coatEta;
-  const int ggx = pm.distribution == GVPM_MICROFACET_GGX;
+  const int dist = pm.distribution;
   const double alpha = pm.exponent, alphaS = alpha * (1.2 - 0.2 * std::sqrt(ci)), alphaSqr = alphaS * alphaS;
-  double tanThetaMSqr, pdfM, cosThetaM;
-  if (ggx) {
+  double tanThetaMSqr, pdfM, cosThetaM, phi = 2.0 * kPi * b;
+  if (dist == GVPM_MICROFACET_PHONG) {
+    samplePhongDist(alphaS, alphaS, a, b, cosThetaM, phi, pdfM);  // (the exponent of the scaled alpha, scaleAlpha :178-183)
+  } else if (dist == GVPM_MICROFACET_GGX) {
     tanThetaMSqr = alphaSqr * a / (1.0 - a);
     cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
     const double temp = 1 + tanThetaMSqr / alphaSqr;
@@ -454,7 +529,7 @@ inline bool sampleDielectric(const SynthMat &pm, V3 n, V3 wi, double a, double b
     pdfM = (1.0 - a) / (kPi * alphaSqr * cosThetaM * cosThetaM * cosThetaM);
   }
   if (!(pdfM >= 1e-20)) return false;
-  const double sinThetaM = std::sqrt(std::fmax(0.0, 1 - cosThetaM * cosThetaM)), phi = 2.0 * kPi * b;
+  const double sinThetaM = std::sqrt(std::fmax(0.0, 1 - cosThetaM * cosThetaM));
   const V3 m = toWorld(nI, V3(sinThetaM * std::cos(phi), sinThetaM * std::sin(phi), cosThetaM));
   const double wiM = dot(wi, m);
   double cosThetaT;
@@ -478,9 +553,9 @@ inline bool sampleDielectric(const SynthMat &pm, V3 n, V3 wi, double a, double b
     dwh = be * be * dot(wo, m) / (sD * sD);
   }
   const double co = dot(nI, wo), woM = dot(wo, m);
-  const double D = conductorD(ggx, alpha, cosThetaM), G = conductorG1(ggx, alpha, ci, wiM) * conductorG1(ggx, alpha, co, woM);
+  const double D = conductorD(dist, alpha, cosThetaM), G = conductorG1(dist, alpha, ci, wiM) * conductorG1(dist, alpha, co, woM);
   weight = weight * std::fabs(D * G * wiM / (pdfM * ci));
-  pdf = conductorD(ggx, alphaS, cosThetaM) * cosThetaM * (reflect ? F : 1 - F) * std::fabs(dwh);
+  pdf = conductorD(dist, alphaS, cosThetaM) * cosThetaM * (reflect ? F : 1 - F) * std::fabs(dwh);
   return maxc(weight) > 0 && pdf > 0;
 }
 
@@ -525,11 +600,12 @@ inline bool samplePlastic(const SynthMat &pm, V3 n, V3 wi, double a, double b, V
       }
     }
     if (choseSpecular) {
-      double tanThetaMSqr;
-      if (pm.distribution == GVPM_MICROFACET_GGX) tanThetaMSqr = alphaSqr * a / (1.0 - a);
-      else tanThetaMSqr = alphaSqr * -std::log(1.0 - a);
-      const double cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
-      const double sinThetaM = std::sqrt(std::fmax(0.0, 1 - cosThetaM * cosThetaM)), phi = 2.0 * kPi * sy;
+      // (the half vector's own pdf is not needed: the bounce's pdf comes from D below)
+      double cosThetaM, phi = 2.0 * kPi * sy, pdfM;
+      if (pm.distribution == GVPM_MICROFACET_PHONG) samplePhongDist(alpha, alpha, a, sy, cosThetaM, phi, pdfM);
+      else if (pm.distribution == GVPM_MICROFACET_GGX) cosThetaM = 1.0 / std::sqrt(1.0 + alphaSqr * a / (1.0 - a));
+      else cosThetaM = 1.0 / std::sqrt(1.0 + alphaSqr * -std::log(1.0 - a));
+      const double sinThetaM = std::sqrt(std::fmax(0.0, 1 - cosThetaM * cosThetaM));
       const V3 m = toWorld(n, V3(sinThetaM * std::cos(phi), sinThetaM * std::sin(phi), cosThetaM));
       wo = m * (2.0 * dot(wi, m)) - wi;
       comp = 0x00008u;  // EGlossyReflection
@@ -772,38 +848,7 @@ template <class PATH> GVPM_HD inline bool walkStep(const SceneView &sc, Philox &
         cur.pdf = pdfW;
         if (maxc(cur.weight) <= 0) return false;
       } else if (cur.matKind == MAT_ROUGHCONDUCTOR) {
-        // RoughConductor::sample, sampleVisible = false (roughconductor.cpp:321-389 with MicrofacetDistribution::sampleAll,
-        // microfacet.h:287-347): half vector m ~ D cos, wo = reflect(wi, m), weight = F D G (wi . m) / (pdf_m cos_i),
-        // pdf = pdf_m / (4 |wo . m|)
-        const SynthMat &pm = sc.mats[cur.mat];
-        const double alpha = pm.exponent, alphaSqr = alpha * alpha, cosWi = dot(cur.n, wi);
-        double tanThetaMSqr, pdfM, cosThetaM;
-        if (pm.distribution == GVPM_MICROFACET_GGX) {
-          tanThetaMSqr = alphaSqr * a / (1.0 - a);
-          cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
-          const double temp = 1 + tanThetaMSqr / alphaSqr;
-          pdfM = kInvPi / (alphaSqr * cosThetaM * cosThetaM * cosThetaM * temp * temp);
-        } else {
-          tanThetaMSqr = alphaSqr * -std::log(1.0 - a);
-          cosThetaM = 1.0 / std::sqrt(1.0 + tanThetaMSqr);
-          pdfM = (1.0 - a) / (kPi * alphaSqr * cosThetaM * cosThetaM * cosThetaM);
-        }
-        if (!(pdfM >= 1e-20)) return false;
-        const double sinThetaM = std::sqrt(std::fmax(0.0, 1 - cosThetaM * cosThetaM)), phi = 2.0 * kPi * b;
-        const V3 m = toWorld(cur.n, V3(sinThetaM * std::cos(phi), sinThetaM * std::sin(phi), cosThetaM));
-        const double wiM = dot(wi, m);
-        wo = m * (2.0 * wiM) - wi;
-        const double cosWo = dot(cur.n, wo);
-        if (cosWo <= 0) return false;
-        const double woM = dot(wo, m);
-        const double D = conductorD(pm.distribution, alpha, cosThetaM);
-        const double G = conductorG1(pm.distribution, alpha, cosWi, wiM) * conductorG1(pm.distribution, alpha, cosWo, woM);
-        const double wgt = D * G * wiM / (pdfM * cosWi);
-        cur.weight = V3(conductorFresnel(wiM, pm.eta.x, pm.k.x) * pm.spec.x, conductorFresnel(wiM, pm.eta.y, pm.k.y) * pm.spec.y,
-                        conductorFresnel(wiM, pm.eta.z, pm.k.z) * pm.spec.z) * wgt;
-        cur.pdf = pdfM / (4.0 * std::fabs(woM));
-        cur.comp = 0x00008u;  // EGlossyReflection
-        if (maxc(cur.weight) <= 0 || !(cur.pdf > 0)) return false;
+        if (!sampleConductor(sc.mats[cur.mat], cur.n, wi, a, b, wo, cur.weight, cur.pdf, cur.comp)) return false;
       } else if (cur.matKind == MAT_WARD_ANISO || cur.matKind == MAT_ROUGHCONDUCTOR_ANISO) {
         if (!sampleAniso(sc.mats[cur.mat], cur.n, wi, a, b, wo, cur.weight, cur.pdf, cur.comp)) return false;
       } else if (cur.matKind == MAT_ROUGHPLASTIC || cur.matKind == MAT_PLASTIC) {

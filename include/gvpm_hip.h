@@ -192,8 +192,10 @@ typedef struct gvpm_medium {
  *     reconnection evaluates THAT component (bRec.component = sampledComponentIndex): eval = its term alone, pdf = its pdf
  *     times pdfComponent (w or 1 - w, :331-342) -- which is the matching term of the mixture above.  Such a vertex names an
  *     entry whose `distribution` field holds component + 1 (0: both, the entries of round 4; 1: specular only; 2: diffuse
- *     only): a surface that can be met both ways has one entry per way.
- *   GVPM_BSDF_ROUGHCONDUCTOR  src/bsdfs/roughconductor.cpp with an ISOTROPIC Beckmann or GGX distribution (alphaU == alphaV:
+ *     only): a surface that can be met both ways has one entry per way.  gvpm_upload_bsdfs does not range-check the field for this
+ *     kind: any value other than 1 and 2 reads as both components (GVPM_MICROFACET_PHONG = 3 among them: it is NOT read as a
+ *     microfacet distribution here, and is accepted).
+ *   GVPM_BSDF_ROUGHCONDUCTOR  src/bsdfs/roughconductor.cpp with an ISOTROPIC Beckmann, GGX or Phong distribution (alphaU == alphaV:
  *     the photon record carries the parent's normal, not its tangent frame) -- one component, EGlossyReflection:
  *       H = normalize(wi + wo), D = MicrofacetDistribution::eval (microfacet.h:191-232), G = smithG1(wi, H) smithG1(wo, H)
  *       (:477-522), F = fresnelConductorExact(wi . H, eta, k) * specular (libcore/util.cpp:747-769)
@@ -201,6 +203,12 @@ typedef struct gvpm_medium {
  *       pdf(wi, wo)  = D smithG1(wi, H) / (4 cos(theta_i))  [sample_visible]   or   D cos(theta_H) / (4 |wo . H|)  :295-319
  *     both zero unless cos(theta_i), cos(theta_o) > 0; pdfComponent = 1.  `exponent` carries alpha (after the constructor's
  *     clamp to >= 1e-4, microfacet.h:135-136).  Classified like any vertex by its roughness alpha against bounceRoughness.
+ *     THE PHONG DISTRIBUTION (GVPM_MICROFACET_PHONG; the same for every kind that has a `distribution`): with the exponent
+ *     e(alpha) = max(2 / alpha^2 - 2, 0) (microfacet.h:700-704),
+ *       D(m) = (e + 2) / (2 pi) cos(theta_m)^e,  0 for cos(theta_m) <= 0;  D cos(theta_m) < 1e-20 -> D = 0          (:191-232)
+ *       smithG1 = Beckmann's rational form, with alpha and not the exponent                                          (:489-501)
+ *     and the pdf is the all-normals form alone: the reference forces sampleVisible off for this distribution (:140-144), and
+ *     `sample_visible` != 0 with it is refused (GVPM_ERR_INVALID_ARG).
  *   GVPM_BSDF_WARD (round 5)  src/bsdfs/ward.cpp with alphaU == alphaV (isotropic: the photon record carries the parent's normal,
  *     not its tangent frame) and roughness alpha >= 0.05, i.e. BOTH components (Ward::sampleComponent, ward.cpp:370-389): with
  *     H = wi + wo (NOT normalised, as the reference has it), tan2 = (|H|^2 - H.z^2) / H.z^2, E = exp(-tan2 / alpha^2),
@@ -210,7 +218,7 @@ typedef struct gvpm_medium {
  *                 = |H|^2 / (pi alpha^2 H.z^4)                variant 2, "balanced" (the plugin's default)
  *       pdf  = w E / (4 pi alpha^2 (Hn . wi) cos^3(theta_Hn)) + (1 - w) cos(theta_o) / pi,  Hn = H / |H|                :230-266
  *     `exponent` carries alpha, `sample_visible` the variant, `specular_sampling_weight` w; pdfComponent = 1.
- *   GVPM_BSDF_ROUGHPLASTIC  src/bsdfs/roughplastic.cpp:326-437,532-586 with an isotropic, untextured Beckmann or GGX distribution:
+ *   GVPM_BSDF_ROUGHPLASTIC  src/bsdfs/roughplastic.cpp:326-437,532-586 with an isotropic, untextured Beckmann, GGX or Phong distribution:
  *     a dielectric coating (component 0, EGlossyReflection) over a diffuse base (component 1, EDiffuseReflection).  With
  *     H = normalize(wi + wo), D, G as for the rough conductor, F = fresnelDielectricExt(wi . H, eta) (libcore/util.cpp:659-689),
  *     T(c) = the external rough transmittance at the surface's eta and alpha (rtrans.h:183-236 after setEta / setAlpha: 100
@@ -222,7 +230,8 @@ typedef struct gvpm_medium {
  *       pdf(wi, wo)  = pS pdf_m + (1 - pS) cos(theta_o) / pi,  pdf_m = the rough conductor's pdf (either form)
  *     both zero unless cos(theta_i), cos(theta_o) > 0.  Below roughness 0.05 sampleNext picks ONE component (sampleComponent,
  *     :532-564) and the reconnection evaluates that component: eval = its term alone, pdf * pdfComponent = its term of the
- *     mixture above (pdfComponent = pS or 1 - pS, :566-586).  Fields: `specular`, `exponent` = alpha (>= 1e-4), `distribution`,
+ *     mixture above (pdfComponent = pS or 1 - pS, :566-586).  With GVPM_MICROFACET_PHONG, D and G are the rough conductor's for that
+ *     distribution, pdf_m = D cos(theta_H) / (4 |wo . H|), and the slice is the one of data/microfacet/phong.dat.  Fields: `specular`, `exponent` = alpha (>= 1e-4), `distribution`,
  *     `sample_visible`, `specular_sampling_weight` as for the rough conductor; eta[0] = eta (>= 1), eta[1] = Fdr (in [0, 1)),
  *     k[0] = the component met, as a float: 0 both, 1 the glossy one alone, 2 the diffuse one alone (sampledComponentIndex + 1);
  *     k[1] = 1 for `nonlinear`, else 0; the rest zero.  THE SLICE follows the entry in the table: the 7 entries behind a
@@ -253,16 +262,20 @@ typedef struct gvpm_medium {
  *         e = (m.x^2 / alphaU^2 + m.y^2 / alphaV^2) / cos^2(theta_m);  D cos(theta_m) < 1e-20 -> D = 0           (microfacet.h:191-232)
  *         smithG1(v, m) with alpha = projectRoughness(v) = sqrt((v.x^2 alphaU^2 + v.y^2 alphaV^2) / sin^2(theta_v))    (:477-522, :541-551)
  *         (perpendicular incidence returns 1 before the projection), Fresnel and both forms of the pdf as for the isotropic kind.
+ *         D = sqrt((eU + 2)(eV + 2)) / (2 pi) cos(theta_m)^e  [GVPM_MICROFACET_PHONG: Ashikhmin-Shirley], eU = e(alphaU), eV = e(alphaV),
+ *         e = eU where alphaU == alphaV or sin^2(theta_m) <= 2^-128 (RCPOVERFLOW, constants.h:58), else
+ *         e = (eU m.x^2 + eV m.y^2) / sin^2(theta_m) (:553-565); the same cut; smithG1 is Beckmann's at the projected roughness;
+ *         the all-normals pdf alone.
  *     gvpm_upload_bsdfs refuses, before anything is copied (GVPM_ERR_INVALID_ARG): a head without its frame entry; a frame
  *     word that is not +0 or a normal float (-0, subnormals, NaN, inf: a raw entry read as a head then shows 0 or a word
  *     >= 2^23 as its kind, never a valid one); | |s| - 1 | > 1e-3; alphaU or alphaV < 1e-4 (the microfacet constructor's clamp,
  *     microfacet.h:88-90; for Ward, whose plugin has no clamp, it is THIS LIBRARY's own limit); Ward: 0.5 (alphaU + alphaV) <
  *     0.05 (Ward::getRoughness, ward.cpp:365, against sampleComponent, :370-389: below it one component is sampled), a
  *     sampling weight outside [0, 1]; GVPM_ERR_UNSUPPORTED: a Ward variant outside 0..2 or `distribution` != 0, a conductor
- *     whose distribution is not Beckmann or GGX (the Phong / Ashikhmin-Shirley one).  alphaU == alphaV is legal: the isotropic
+ *     whose distribution is not Beckmann, GGX or Phong / Ashikhmin-Shirley.  alphaU == alphaV is legal: the isotropic
  *     kind, whatever the tangent.  Photons name HEAD indices only.  GVPM_ANISO_ENTRIES = the raw entries behind such a head.
  *     (7 is not a kind.)
- *   GVPM_BSDF_ROUGHDIELECTRIC  src/bsdfs/roughdielectric.cpp:270-422 with an isotropic, untextured Beckmann or GGX distribution: the
+ *   GVPM_BSDF_ROUGHDIELECTRIC  src/bsdfs/roughdielectric.cpp:270-422 with an isotropic, untextured Beckmann, GGX or Phong distribution: the
  *     one kind that TRANSMITS.  RoughDielectric::sampleComponent returns -1 and pdfComponent 1 at every roughness (:647-657), so
  *     there is no entry per component: reflection and transmission are both in play at every vertex.  Two conventions:
  *     (1) THE RECORD'S NORMAL POINTS TO THE SIDE THE PHOTON LEFT: for a record that names an entry of this kind, parent_n is the
@@ -288,7 +301,8 @@ typedef struct gvpm_medium {
  *       (:477-522: dot(v, m) cosTheta(v) <= 0 gives 0),
  *       pdf = |prob dwh_dwo| (reflection: F, transmission: 1 - F)                                                   (:350-422)
  *         prob = D smithG1(wi, H) |wi . H| / ci  [sample_visible]   or   D' cos(theta_H), D' = the distribution at alpha scaled by
- *         1.2 - 0.2 sqrt(ci) (:406-414), with its own D' cos(theta_H) < 1e-20 -> 0 cut.
+ *         1.2 - 0.2 sqrt(ci) (:406-414), with its own D' cos(theta_H) < 1e-20 -> 0 cut.  GVPM_MICROFACET_PHONG: D as for the rough
+ *         conductor, prob = D' cos(theta_H) alone, D' with the exponent recomputed from the scaled alpha (scaleAlpha, microfacet.h:178-183).
  *     D == 0 gives eval = 0, and pdf = 0 with visible normals; without them the pdf is D''s (RoughDielectric::pdf does not look at
  *     D): a half vector between the two cuts is a shift that succeeds with zero flux.  The same holds where G = 0 (a direction no
  *     facet reaches, a facet seen from behind): eval = 0, pdf > 0.  |wi + wo eta|^2 < 1e-12 (no half vector) is a failed shift.
@@ -296,7 +310,8 @@ typedef struct gvpm_medium {
  *     `exponent` = alpha (>= 1e-4), `distribution`, `sample_visible` as for the rough conductor, eta[0] as above; eta[1], eta[2],
  *     `specular_sampling_weight` and `reserved` zero.  No raw entries behind the head.  gvpm_upload_bsdfs refuses, before anything
  *     is copied (GVPM_ERR_INVALID_ARG): alpha < 1e-4, eta[0] not finite or outside [0.2, 5], a reflectance or transmittance
- *     channel outside [0, 1], a non-zero word where zero is asked; GVPM_ERR_UNSUPPORTED: a distribution that is not Beckmann or GGX.
+ *     channel outside [0, 1], a non-zero word where zero is asked, `sample_visible` != 0 with
+ *     GVPM_MICROFACET_PHONG; GVPM_ERR_UNSUPPORTED: a distribution that is not Beckmann, GGX or Phong.
  *   A record of any OTHER kind with cos(theta_i) <= 0 fails its shift, as ever.
  * A surface parent outside the closed set stays what it was: the host flags the photon's shift type 0 (failed shift).   */
 enum { GVPM_BSDF_PHONG = 1, GVPM_BSDF_ROUGHCONDUCTOR = 2, GVPM_BSDF_WARD = 3, GVPM_BSDF_ROUGHPLASTIC = 4, GVPM_BSDF_PLASTIC = 5,
@@ -305,7 +320,9 @@ enum { GVPM_BSDF_PHONG = 1, GVPM_BSDF_ROUGHCONDUCTOR = 2, GVPM_BSDF_WARD = 3, GV
 #define GVPM_RTRANS_KNOTS 100          /* values of a rough-plastic slice                                          */
 #define GVPM_RTRANS_ENTRIES 7          /* raw table entries behind a rough-plastic head (448 bytes)                */
 enum { GVPM_WARD_WARD = 0, GVPM_WARD_DUER = 1, GVPM_WARD_BALANCED = 2 };
-enum { GVPM_MICROFACET_BECKMANN = 0, GVPM_MICROFACET_GGX = 1 };
+/* GVPM_MICROFACET_PHONG: the Phong distribution and, with alphaU != alphaV, Ashikhmin-Shirley's (MicrofacetDistribution::EPhong is 2
+ * in microfacet.h:56: the binding maps it).  (2 is not a distribution: gvpm_upload_bsdfs refuses it, GVPM_ERR_UNSUPPORTED.) */
+enum { GVPM_MICROFACET_BECKMANN = 0, GVPM_MICROFACET_GGX = 1, GVPM_MICROFACET_PHONG = 3 };
 typedef struct gvpm_bsdf {    /* 64 bytes */
   int32_t kind;               /* GVPM_BSDF_*                                                            */
   float specular[3];          /* m_specularReflectance (Phong: after ensureEnergyConservation, phong.cpp:86-91) */

@@ -494,6 +494,18 @@ private:
                                                                                its entry in the table of gvpm_upload_bsdfs */
   }
 
+  /* MicrofacetDistribution::EType (microfacet.h:50-57) as GVPM_MICROFACET_*: EPhong is 2 there and 3 here (2 is not a distribution,
+   * include/gvpm_hip.h); -1: a type the library does not know.  getSampleVisible() is false for EPhong (:140-144), as the library
+   * demands.                                                                                                                     */
+  static int microfacetCode(MicrofacetDistribution::EType type) {
+    switch (type) {
+      case MicrofacetDistribution::EBeckmann: return GVPM_MICROFACET_BECKMANN;
+      case MicrofacetDistribution::EGGX: return GVPM_MICROFACET_GGX;
+      case MicrofacetDistribution::EPhong: return GVPM_MICROFACET_PHONG;
+      default: return -1;
+    }
+  }
+
   /* A surface parent whose BSDF is in the device's table of glossy BSDFs (include/gvpm_hip.h, gvpm_bsdf).  Returns its index
    * (appending the entry on first sight), -1 for every other vertex.
    * Phong (src/bsdfs/phong.cpp), not textured: sampled with BOTH components (sampledComponentIndex == -1: what
@@ -501,7 +513,7 @@ private:
    * phong.cpp:311-330) or -- round 5 -- through ONE of them (0 specular, 1 diffuse): an entry per (BSDF, component), its
    * `distribution` field = component + 1 (include/gvpm_hip.h).  The exponent and the sampling weight have no getters: they are read back through getRoughness =
    * sqrt(2 / (2 + exponent)) (phong.cpp:293-300) and pdfComponent(component 0) = m_specularSamplingWeight (:332-343).
-   * RoughConductor (src/bsdfs/roughconductor.cpp), not textured, isotropic Beckmann or GGX, whose Properties name `eta` and `k`
+   * RoughConductor (src/bsdfs/roughconductor.cpp), not textured, isotropic Beckmann, GGX or Phong, whose Properties name `eta` and `k`
    * themselves (a `material` preset keeps its spectra in protected members: such a surface stays outside the closed set):
    * m_eta = eta / extEta, m_k = k / extEta (:181-191), alpha and the distribution through MicrofacetDistribution(props) as the
    * constructor reads them (:193-201).                                                                                    */
@@ -562,11 +574,11 @@ private:
       const Properties &props = bsdf->getProperties();
       if (!props.hasProperty("eta") || !props.hasProperty("k")) return -1;
       MicrofacetDistribution distr(props);
-      if (!distr.isIsotropic() || (distr.getType() != MicrofacetDistribution::EBeckmann && distr.getType() != MicrofacetDistribution::EGGX))
+      if (!distr.isIsotropic() || microfacetCode(distr.getType()) < 0)
         return -1;
       b.kind = GVPM_BSDF_ROUGHCONDUCTOR;
       b.exponent = (float) distr.getAlphaU();
-      b.distribution = distr.getType() == MicrofacetDistribution::EGGX ? GVPM_MICROFACET_GGX : GVPM_MICROFACET_BECKMANN;
+      b.distribution = microfacetCode(distr.getType());
       b.sample_visible = distr.getSampleVisible() ? 1 : 0;
       const Float extEta = lookupIOR(props, "extEta", "air");
       const Spectrum eta = props.getSpectrum("eta") / extEta, k = props.getSpectrum("k") / extEta;
@@ -583,7 +595,7 @@ private:
   }
   /* Anisotropic Ward (both components: 0.5 (alphaU + alphaV) >= 0.05, ward.cpp:365,370-389 -- glossyIndex() has checked
    * sampledComponentIndex == -1; alphaU / alphaV from the plugin's properties as its constructor reads them, :115-129) and
-   * anisotropic Beckmann / GGX rough conductors whose Properties name `eta` and `k`.  The head has the isotropic kind's
+   * anisotropic Beckmann / GGX / Ashikhmin-Shirley rough conductors whose Properties name `eta` and `k`.  The head has the isotropic kind's
    * fields with exponent = alphaU; the frame entry behind it holds the vertex's shFrame.s (world space) and alphaV.        */
   enum { GVPM_SHIM_MAX_TANGENTS = 4 };
   int anisoIndex(const PathVertex *par, const Intersection &its, const BSDF *bsdf, bool ward) {
@@ -620,11 +632,11 @@ private:
     } else {
       if (!props.hasProperty("eta") || !props.hasProperty("k")) return -1;
       MicrofacetDistribution distr(props);
-      if (distr.getType() != MicrofacetDistribution::EBeckmann && distr.getType() != MicrofacetDistribution::EGGX) return -1;
+      if (microfacetCode(distr.getType()) < 0) return -1;
       alphaU = distr.getAlphaU();   /* (after the constructor's clamp to >= 1e-4, microfacet.h:88-90) */
       alphaV = distr.getAlphaV();
       b.kind = GVPM_BSDF_ROUGHCONDUCTOR_ANISO;
-      b.distribution = distr.getType() == MicrofacetDistribution::EGGX ? GVPM_MICROFACET_GGX : GVPM_MICROFACET_BECKMANN;
+      b.distribution = microfacetCode(distr.getType());
       b.sample_visible = distr.getSampleVisible() ? 1 : 0;
       const Float extEta = lookupIOR(props, "extEta", "air");
       const Spectrum eta = props.getSpectrum("eta") / extEta, k = props.getSpectrum("k") / extEta;
@@ -650,7 +662,7 @@ private:
   std::map<std::pair<const BSDF *, std::array<int, 3>>, uint32_t> m_anisoIndex;   /* (BSDF, quantised shFrame.s) -> head */
   std::map<const BSDF *, int> m_anisoTangents;   /* distinct tangents seen per BSDF; -1: too many, refused for good */
   /* RoughPlastic (src/bsdfs/roughplastic.cpp; untextured -- the ESpatiallyVarying test above -- so alpha is constant and
-   * isotropic, Beckmann or GGX) and the DIFFUSE component of SmoothPlastic (src/bsdfs/plastic.cpp; its Dirac component is a
+   * isotropic, Beckmann, GGX or Phong) and the DIFFUSE component of SmoothPlastic (src/bsdfs/plastic.cpp; its Dirac component is a
    * specular vertex: -1).  An entry per (BSDF, sampled component): k[0] = sampledComponentIndex + 1.  eta = intIOR / extIOR as
    * the constructors read them (roughplastic.cpp:203-213, plastic.cpp: the same two lookups); w = lum(ks) / (lum(kd) + lum(ks))
    * (roughplastic.cpp:275-277) from the two reflectances; rough: the slice by building a RoughTransmittance as configure()
@@ -681,11 +693,11 @@ private:
     Float Ftr;
     if (rough) {
       MicrofacetDistribution distr(props);
-      if (!distr.isIsotropic() || (distr.getType() != MicrofacetDistribution::EBeckmann && distr.getType() != MicrofacetDistribution::EGGX))
+      if (!distr.isIsotropic() || microfacetCode(distr.getType()) < 0)
         return -1;
       const Float alpha = distr.getAlphaU();
       b.exponent = (float) alpha;
-      b.distribution = distr.getType() == MicrofacetDistribution::EGGX ? GVPM_MICROFACET_GGX : GVPM_MICROFACET_BECKMANN;
+      b.distribution = microfacetCode(distr.getType());
       b.sample_visible = distr.getSampleVisible() ? 1 : 0;
       ref<RoughTransmittance> ext = new RoughTransmittance(distr.getType());
       ref<RoughTransmittance> inte = ext->clone();
@@ -732,7 +744,7 @@ private:
     if (found != m_bsdfIndex.end()) return (int) found->second;
     const Properties &props = bsdf->getProperties();
     MicrofacetDistribution distr(props);
-    if (!distr.isIsotropic() || (distr.getType() != MicrofacetDistribution::EBeckmann && distr.getType() != MicrofacetDistribution::EGGX))
+    if (!distr.isIsotropic() || microfacetCode(distr.getType()) < 0)
       return -1;
     const Float eta = lookupIOR(props, "intIOR", "bk7") / lookupIOR(props, "extIOR", "air");
     if (!(eta >= 0.2f && eta <= 5.f)) return -1;   /* (gvpm_upload_bsdfs takes [0.2, 5] for either side)                    */
@@ -740,7 +752,7 @@ private:
     memset(&b, 0, sizeof(b));
     b.kind = GVPM_BSDF_ROUGHDIELECTRIC;
     b.exponent = (float) distr.getAlphaU();
-    b.distribution = distr.getType() == MicrofacetDistribution::EGGX ? GVPM_MICROFACET_GGX : GVPM_MICROFACET_BECKMANN;
+    b.distribution = microfacetCode(distr.getType());
     b.sample_visible = distr.getSampleVisible() ? 1 : 0;
     b.eta[0] = (float) (inside ? 1 / eta : eta);
     Spectrum ks = props.getSpectrum("specularReflectance", Spectrum(1.0f)), kt = props.getSpectrum("specularTransmittance", Spectrum(1.0f));
