@@ -165,6 +165,8 @@ GVPM_RTRANS_KNOTS, GVPM_RTRANS_ENTRIES = 100, 7
 GVPM_BSDF_WARD_ANISO, GVPM_BSDF_ROUGHCONDUCTOR_ANISO = 6, 8   # (7 is not a kind)
 GVPM_ANISO_ENTRIES = 1
 GVPM_BSDF_ROUGHDIELECTRIC = 9   # (no raw entries behind the head; one entry per side of incidence)
+GVPM_BSDF_MIXTURE = 10          # (no raw entries behind the head; one entry per component met)
+GVPM_MIXTURE_CHILD_DIFFUSE, GVPM_MIXTURE_CHILD_ABSENT = -1, -2
 
 
 def bsdf_tail_entries(kind):
@@ -228,6 +230,17 @@ def dielectric_entry(specular, transmittance, alpha, eta, distribution=0, sample
     b["kind"], b["specular"], b["k"], b["exponent"] = GVPM_BSDF_ROUGHDIELECTRIC, specular, transmittance, alpha
     b["distribution"], b["sample_visible"] = distribution, sample_visible
     b["eta"][0, 0] = eta
+    return b
+
+
+def mixture_entry(weights, children, component=0):
+    """one GVPM_BSDF_MIXTURE entry (include/gvpm_hip.h): `weights` = (w_0, w_1) after the reference's rescale, `children` = for each
+    child the table index of its rough-conductor head, GVPM_MIXTURE_CHILD_DIFFUSE (the Lambertian: the record's parent_scat) or
+    GVPM_MIXTURE_CHILD_ABSENT (not evaluable on the device); `component` = the sampled component + 1 (0: both children)"""
+    b = np.zeros(1, BSDF_DTYPE)
+    b["kind"], b["distribution"] = GVPM_BSDF_MIXTURE, component
+    b["specular"][0, :2] = weights
+    b["eta"][0, :2] = children
     return b
 
 

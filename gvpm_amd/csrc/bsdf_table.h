@@ -67,12 +67,25 @@ GVPM_TBL bool bsdfDielectricZerosValid(const gvpm_bsdf &b) {
   return (bsdfBits(b.eta[1]) | bsdfBits(b.eta[2]) | bsdfBits(b.specular_sampling_weight) | bsdfBits(b.reserved[0]) | bsdfBits(b.reserved[1])) == 0u;
 }
 
+// the mixture: a weight is finite and not negative (their sum > 0 is the caller's test); a child word is GVPM_MIXTURE_CHILD_DIFFUSE,
+// GVPM_MIXTURE_CHILD_ABSENT or a table index below n, as an integer-valued float; every word the kind leaves unused is +0
+GVPM_TBL bool bsdfMixtureWeightValid(float w) { return w >= 0.f && w <= FLT_MAX; }
+GVPM_TBL bool bsdfMixtureChildValid(float c, uint32_t n) {
+  return c == (float)GVPM_MIXTURE_CHILD_DIFFUSE || c == (float)GVPM_MIXTURE_CHILD_ABSENT ||
+         (bsdfBits(c) == 0u || (c > 0.f && c < (float)n && c == (float)(uint32_t)c));
+}
+GVPM_TBL bool bsdfMixtureZerosValid(const gvpm_bsdf &b) {
+  return (bsdfBits(b.specular[2]) | bsdfBits(b.exponent) | bsdfBits(b.specular_sampling_weight) | (uint32_t)b.sample_visible |
+          bsdfBits(b.eta[2]) | bsdfBits(b.k[0]) | bsdfBits(b.k[1]) | bsdfBits(b.k[2]) | bsdfBits(b.reserved[0]) | bsdfBits(b.reserved[1])) == 0u;
+}
+
 // ---- a head's four rows ----
 //   row 0  {kind, specular.rgb}
 //   row 1  {exponent | alpha (alphaU), sampling weight, distribution | Phong component, sample_visible | Ward variant}
 //   row 2  {eta.rgb, k.r}         plastics: {eta, Fdr, -, component met}
 //   row 3  {k.g, k.b, 0, 0}       plastics: {nonlinear, ...}
 //   rough dielectric: row 2 {eta seen from wi's side, 0, 0, transmittance.r}, row 3 {transmittance.g, transmittance.b, 0, 0}
+//   mixture: row 0 {kind, w_0, w_1, 0}, row 1 {0, 0, sampled component + 1, 0}, row 2 {child 0, child 1, 0, 0}
 // The integers travel as their bit patterns, the plastics' component and nonlinear flag as the floats they are in gvpm_bsdf.
 // The readers return a lane as it is stored and leave `!= 0` / `(int)` to the caller where the caller had them: moving such a
 // conversion into the reader changed the kernels' register allocation (NOTEBOOK.md, "one home for the BSDF table").
@@ -105,6 +118,10 @@ template <class R> GVPM_TBL bool bsdfPlasticNonlinear(const R &r3) { return r3.x
 // rows 2 and 3, the rough dielectric: the relative index seen from wi's side, channel C of the specular transmittance
 template <class R> GVPM_TBL float bsdfDielectricEta(const R &r2) { return r2.x; }
 template <int C, class R> GVPM_TBL float bsdfTransmittance(const R &r2, const R &r3) { return C == 0 ? r2.w : (C == 1 ? r3.x : r3.y); }
+// the mixture: weight and child word I (0 or 1), the component met
+template <int I, class R> GVPM_TBL float bsdfMixtureWeight(const R &r0) { return I == 0 ? r0.y : r0.z; }
+template <int I, class R> GVPM_TBL float bsdfMixtureChild(const R &r2) { return I == 0 ? r2.x : r2.y; }
+template <class R> GVPM_TBL int bsdfMixtureComponent(const R &r1) { return (int)bsdfBits(r1.z); }  // 0 both, 1 child 0, 2 child 1
 // the frame entry behind an anisotropic head, as one row: {tangent.xyz, alphaV}
 template <class R> GVPM_TBL float bsdfFrameAlphaV(const R &fr) { return fr.w; }
 

@@ -375,6 +375,7 @@ struct gvpm_context {
   std::vector<gvpm_material> materialsHost;  // what the device table holds (append-only growth needs no stream sync)
   DevBuf<float4> bsdfs;             // gvpm_upload_bsdfs: 4 float4 per glossy surface BSDF (device_types.h, GatherArgs::bsdfs)
   uint32_t nbsdfs = 0;
+  bool bsdfMixtures = false;  // the table holds GVPM_BSDF_MIXTURE heads: G-BRE evaluates with evaluate_bre_mix_kernel
   gvpm_sensor sensor{};             // gvpm_upload_sensor: what the compact beam sets are decoded with
   bool haveSensor = false;
   // photons: raw upload (owned copies or borrowed device pointers) and the built grid

@@ -124,6 +124,9 @@ struct ExEntry {
 };
 static_assert(sizeof(ExEntry) == 512, "ExEntry is 512 bytes");
 
+// cfg.reserved[0] of the arguments carries the library's own switches (GVPM_DEBUG_FLAGS, gvpm_api.hip: 16, 32, 64, 128); this bit is set
+// per gather where the uploaded BSDF table holds a GVPM_BSDF_MIXTURE head: G-BRE then launches evaluate_bre_mix_kernel
+#define GVPM_TABLE_HAS_MIXTURE 256
 struct GatherArgs {
   // photons
   const float4 *hot;

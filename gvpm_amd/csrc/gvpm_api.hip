@@ -383,7 +383,7 @@ static int checkBsdfTail(gvpm_context *h, const gvpm_bsdf *table, uint32_t i, ui
 }
 
 // The rules of head i and of what follows it, in the order they are reported.
-static int checkBsdf(gvpm_context *h, const gvpm_bsdf *table, uint32_t i, uint32_t n) {
+static int checkBsdf(gvpm_context *h, const gvpm_bsdf *table, uint32_t i, uint32_t n, const std::vector<uint8_t> &isHead) {
   using namespace gvpm;
   const gvpm_bsdf &b = table[i];
   const bool weightOk = bsdfWeightValid(b.specular_sampling_weight);
@@ -450,10 +450,34 @@ static int checkBsdf(gvpm_context *h, const gvpm_bsdf *table, uint32_t i, uint32
       return fail(h, GVPM_ERR_INVALID_ARG, "rough dielectric: eta[1], eta[2], the sampling weight and the reserved words are zero");
     if (!bsdfMicrofacetValid(b)) return fail(h, GVPM_ERR_UNSUPPORTED, "rough dielectric: Beckmann, GGX or Phong");
     if (!bsdfSampleVisibleValid(b)) return fail(h, GVPM_ERR_INVALID_ARG, "rough dielectric: the Phong / Ashikhmin-Shirley distribution samples all normals (sample_visible = 0)");
+  } else if (b.kind == GVPM_BSDF_MIXTURE) {
+    // (include/gvpm_hip.h: specular[0..1] = the weights, distribution = the component met + 1, eta[0..1] = the children)
+    if (!bsdfMixtureWeightValid(b.specular[0]) || !bsdfMixtureWeightValid(b.specular[1]) || !(b.specular[0] + b.specular[1] > 0.f) ||
+        !(b.specular[0] + b.specular[1] <= FLT_MAX))
+      return fail(h, GVPM_ERR_INVALID_ARG, "mixture: weights finite and >= 0, their sum > 0");
+    if (b.distribution < 0 || b.distribution > 2) return fail(h, GVPM_ERR_INVALID_ARG, "mixture: component 0 (both) / 1 / 2");
+    if (!bsdfMixtureZerosValid(b))
+      return fail(h, GVPM_ERR_INVALID_ARG, "mixture: specular[2], exponent, the sampling weight, sample_visible, eta[2], k and the reserved words are zero");
+    for (int c = 0; c < 2; ++c) {
+      const float child = b.eta[c];
+      if (!bsdfMixtureChildValid(child, n))
+        return fail(h, GVPM_ERR_INVALID_ARG, "mixture: a child is -1 (Lambertian), -2 (absent) or the index of a head of the table");
+      if (child >= 0.f && !isHead[(uint32_t)child]) return fail(h, GVPM_ERR_INVALID_ARG, "mixture: a child index names a raw entry, not a head");
+      if (child == (float)GVPM_MIXTURE_CHILD_ABSENT && (b.distribution == 0 || b.distribution == c + 1))
+        return fail(h, GVPM_ERR_INVALID_ARG, "mixture: an absent child (-2) is legal only where the entry selects the other child");
+    }
+    for (int c = 0; c < 2; ++c) {
+      if (!(b.eta[c] >= 0.f)) continue;
+      const int ck = table[(uint32_t)b.eta[c]].kind;
+      if (ck != GVPM_BSDF_ROUGHCONDUCTOR && ck != GVPM_BSDF_ROUGHCONDUCTOR_ANISO)
+        return fail(h, GVPM_ERR_UNSUPPORTED, "mixture: a child is the Lambertian or a rough conductor (one component each; no mixture as a child)");
+    }
+    if (b.eta[0] == (float)GVPM_MIXTURE_CHILD_DIFFUSE && b.eta[1] == (float)GVPM_MIXTURE_CHILD_DIFFUSE)
+      return fail(h, GVPM_ERR_UNSUPPORTED, "mixture: two Lambertian children are a GVPM_PARENT_SURFACE record of reflectance w_0 kd_0 + w_1 kd_1");
   } else {
     return fail(h, GVPM_ERR_UNSUPPORTED,
                 "bsdf kind outside the device's closed set (Phong, rough conductor, Ward, the plastics, anisotropic Ward / rough conductor, "
-                "rough dielectric)");
+                "rough dielectric, mixture)");
   }
   return GVPM_OK;
 }
@@ -465,8 +489,11 @@ int gvpm_upload_bsdfs(gvpm_context *h, const gvpm_bsdf *table, uint32_t n) {
   if (n > (1u << 24)) return fail(h, GVPM_ERR_INVALID_ARG, "more than 2^24 bsdfs (the index travels as a float)");
   // four quads per entry (bsdf_table.h); the raw entries behind a head travel as they are
   std::vector<float4> rows(4 * (size_t)n + 4);
+  // which entries are heads (a mixture's children name heads only): the walk of the loop below
+  std::vector<uint8_t> isHead(n, 0);
+  for (uint32_t i = 0; i < n; i += 1 + (uint32_t)gvpm::bsdfTailEntries(table[i].kind)) isHead[i] = 1;
   for (uint32_t i = 0; i < n; ++i) {
-    if (int rc = checkBsdf(h, table, i, n)) return rc;
+    if (int rc = checkBsdf(h, table, i, n, isHead)) return rc;
     const int tail = gvpm::bsdfTailEntries(table[i].kind);
     gvpm::bsdfPackRows(table[i], &rows[4 * (size_t)i].x);
     memcpy(&rows[4 * (size_t)i + 4], &table[i + 1], tail * sizeof(gvpm_bsdf));
@@ -480,6 +507,8 @@ int gvpm_upload_bsdfs(gvpm_context *h, const gvpm_bsdf *table, uint32_t n) {
   HIP_TRY(h, h->bsdfs.ensure(rows.size()));
   HIP_TRY(h, hipMemcpy(h->bsdfs.p, rows.data(), rows.size() * sizeof(float4), hipMemcpyHostToDevice));
   h->nbsdfs = n;
+  h->bsdfMixtures = false;
+  for (uint32_t i = 0; i < n; ++i) h->bsdfMixtures = h->bsdfMixtures || (isHead[i] && table[i].kind == GVPM_BSDF_MIXTURE);
   return GVPM_OK;
 }
 

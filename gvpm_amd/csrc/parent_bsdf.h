@@ -184,6 +184,91 @@ __device__ __forceinline__ float4 roughDielectricEval(const float4 *__restrict__
   return make_float4(f.x, f.y, f.z, fabsf(prob * dwh) * (reflect ? F : 1.f - F));
 }
 
+// The rough conductor (GVPM_BSDF_ROUGHCONDUCTOR, GVPM_BSDF_ROUGHCONDUCTOR_ANISO; src/bsdfs/roughconductor.cpp:257-319, include/gvpm_hip.h)
+// of head `bi`, whose first two rows the caller has read: eval = F D G / (4 cos_i), pdf = D G1(wi) / (4 cos_i) or D cos_H / (4 |wo . H|).
+// Once, for the kind's own arm of glossyParentEval and for the children of a mixture.  f and pdf arrive zero and stay zero where
+// D == 0 (pdfAll = D cos_H, pdfVisible = D G1 ...).  False: the anisotropic frame is rejected -- a failed shift.
+__device__ __forceinline__ bool roughConductorEval(const GatherArgs &a, uint32_t bi, const float4 b0, const float4 b1, int kind, f3 n, f3 wi,
+                                                   f3 wo, float cosWi, float cosWo, f3 &f, float &pdf) {
+  const float4 b2 = a.bsdfs[4 * bi + 2], b3 = a.bsdfs[4 * bi + 3];
+  const float alpha = bsdfAlpha(b1);
+  const int dist = bsdfDistribution(b1), vis = bsdfSampleVisible(b1) != 0;
+  f3 H = wi + wo;
+  H = H * frsq(dot(H, H));
+  const float cH = dot(H, n), wiH = dot(wi, H), woH = dot(wo, H);
+  float D, alI = alpha, alO = alpha;  // (anisotropic: alphaU = the head's alpha, the roughness projected on wi and on wo)
+  if (kind == GVPM_BSDF_ROUGHCONDUCTOR) {
+    D = microfacetD(dist, alpha, cH);
+  } else {
+    const float4 fr = a.bsdfs[4 * (bi + 1)];
+    f3 s, t;
+    if (!anisoFrame(fr, n, s, t)) return false;
+    D = microfacetDAniso(dist, alpha, bsdfFrameAlphaV(fr), dot(H, s), dot(H, t), cH);
+    if (D != 0.f) {
+      alI = projectRoughness(alpha, bsdfFrameAlphaV(fr), dot(wi, s), dot(wi, t), cosWi);
+      alO = projectRoughness(alpha, bsdfFrameAlphaV(fr), dot(wo, s), dot(wo, t), cosWo);
+    }
+  }
+  if (D == 0.f) return true;  // eval and pdf both zero
+  const float G1i = microfacetG1(dist, alI, cosWi, wiH), G1o = microfacetG1(dist, alO, cosWo, woH);
+  const float model = fdiv(D * G1i * G1o, 4.f * cosWi);
+  f = mk3(fresnelConductor(wiH, bsdfConductorEta<0>(b2), bsdfConductorK<0>(b2, b3)) * bsdfSpecular<0>(b0),
+          fresnelConductor(wiH, bsdfConductorEta<1>(b2), bsdfConductorK<1>(b2, b3)) * bsdfSpecular<1>(b0),
+          fresnelConductor(wiH, bsdfConductorEta<2>(b2), bsdfConductorK<2>(b2, b3)) * bsdfSpecular<2>(b0)) * model;
+  pdf = vis ? fdiv(D * G1i, 4.f * cosWi) : fdiv(D * cH, 4.f * fabsf(woH));
+  return true;
+}
+
+// One conductor child of a mixture: `child` = its word of the head (bsdf_table.h); a word that names no head of a rough conductor --
+// gvpm_upload_bsdfs lets none through -- fails the shift like any unknown index.  f and pdf arrive zero.
+__device__ __forceinline__ bool mixtureChildEval(const GatherArgs &a, float child, f3 n, f3 wi, f3 wo, float cosWi, float cosWo, f3 &f,
+                                                 float &pdf) {
+  const uint32_t ci = (uint32_t)child;
+  if (ci >= a.nbsdfs) return false;
+  const float4 c0 = a.bsdfs[4 * ci], c1 = a.bsdfs[4 * ci + 1];
+  const int ck = bsdfKind(c0);
+  if (ck != GVPM_BSDF_ROUGHCONDUCTOR && ck != GVPM_BSDF_ROUGHCONDUCTOR_ANISO) return false;
+  return roughConductorEval(a, ci, c0, c1, ck, n, wi, wo, cosWi, cosWo, f, pdf);
+}
+
+// The two-component mixture (GVPM_BSDF_MIXTURE; src/bsdfs/mixturebsdf.cpp:177-209,316-319, include/gvpm_hip.h): eval = sum w_i eval_i,
+// pdf = sum p_i pdf_i, p_i = w_i / (w_0 + w_1), over both children or over the one the vertex was sampled through (pdf_c times
+// pdfComponent = p_c: the same term).  A child is the Lambertian (reflectance = the record's kd), the head of a rough conductor, or
+// absent, which contributes nothing (gvpm_upload_bsdfs refuses it where the entry selects it).  A conductor child with D == 0
+// contributes zero and the other child still counts; one whose frame is rejected fails the shift.  STRAIGHT-LINE, child 0's conductor,
+// child 1's, the Lambertian last, and the head's rows read again between them so that nothing but n, wi, wo and the sums lives
+// across a conductor: as a run-time loop over the children it cost the G-BRE evaluation 190 to 280 bytes of scratch per lane, as a
+// __noinline__ function 380 (NOTEBOOK.md, "Mixture parents").
+__device__ __forceinline__ bool mixtureEval(const GatherArgs &a, uint32_t bi, f3 kd, f3 n, f3 wi, f3 wo, float cosWi, float cosWo, f3 &f,
+                                            float &pdf) {
+  {
+    const float child = bsdfMixtureChild<0>(a.bsdfs[4 * bi + 2]);
+    if (bsdfMixtureComponent(a.bsdfs[4 * bi + 1]) != 2 && child >= 0.f && !mixtureChildEval(a, child, n, wi, wo, cosWi, cosWo, f, pdf))
+      return false;
+  }
+  const float4 m0 = a.bsdfs[4 * bi], m1 = a.bsdfs[4 * bi + 1], m2 = a.bsdfs[4 * bi + 2];
+  const int comp = bsdfMixtureComponent(m1);  // 0 both, 1 child 0 alone, 2 child 1 alone
+  const float w0 = bsdfMixtureWeight<0>(m0), w1 = bsdfMixtureWeight<1>(m0), ip = frcp(w0 + w1);
+  f = f * w0;
+  pdf *= w0 * ip;
+  const float child1 = bsdfMixtureChild<1>(m2);
+  if (comp != 1 && child1 >= 0.f) {
+    f3 fc = mk3(0.f);
+    float pc = 0.f;
+    if (!mixtureChildEval(a, child1, n, wi, wo, dot(n, wi), dot(n, wo), fc, pc)) return false;
+    const float4 r0 = a.bsdfs[4 * bi];
+    f = f + fc * bsdfMixtureWeight<1>(r0);
+    pdf += pc * (bsdfMixtureWeight<1>(r0) * frcp(bsdfMixtureWeight<0>(r0) + bsdfMixtureWeight<1>(r0)));
+  }
+  // the Lambertian child in play (at most one: two are refused), diffuse.cpp:110-127
+  const float wl = (comp != 2 && bsdfMixtureChild<0>(m2) == (float)GVPM_MIXTURE_CHILD_DIFFUSE)
+                       ? w0
+                       : ((comp != 1 && child1 == (float)GVPM_MIXTURE_CHILD_DIFFUSE) ? w1 : 0.f);
+  f = f + kd * (INV_PI_F * cosWo * wl);
+  pdf += INV_PI_F * cosWo * (wl * ip);
+  return true;
+}
+
 // A glossy surface parent (GVPM_PARENT_SURFACE_BSDF): BSDF::eval and BSDF::pdf * pdfComponent of the table entry the
 // record names, towards the new direction `wo` (shift_diffuse.cpp:25-41 with bRec.component = -1).  Phong, src/bsdfs/
 // phong.cpp:121-186: eval = (ks (e + 2) / 2pi alpha^e + kd / pi) cos_o, pdf = w alpha^e (e + 1) / 2pi + (1 - w) cos_o / pi,
@@ -191,11 +276,15 @@ __device__ __forceinline__ float4 roughDielectricEval(const float4 *__restrict__
 // / (4 cos_i) or D cos_H / (4 |wo . H|) (include/gvpm_hip.h).  cosWo > 0 and cosWi != 0 is the caller's test; cosWi < 0 (the
 // light arrived on the other side: a transmitted photon) is the rough dielectric's alone, every other kind fails the shift.
 // False: no such entry (a failed shift).
+// MIX: the kernel evaluates mixture entries (GVPM_BSDF_MIXTURE), dispatched LAST.  Everywhere but in the G-BRE evaluation, whose
+// kernels exist in both forms: the one without reads such an entry as no kind, and is launched only where the table holds none
+// (gather_bre.hip, launch_evaluate_bre) -- with the arm inlined the kernel of a plain benchmark run spilled 15 VGPRs where it spills 7.
 // state (optional out, round 5): bit 0 -- the pdf is POSITIVE in double precision although it underflowed here (the
 // specular component of a Phong wall alone, exponent ~1000: alpha^e leaves fp32 below alpha ~ 0.94 and fp64 only below ~0.6;
 // with pdf == 0 the reference fails the shift, with a positive one -- however small -- it succeeds, with weight 1 and a
 // flux that rounds to zero: only the counter tells them apart); bit 1 -- within rounding of the double's own underflow:
 // the exact pass decides, with the lobe in fp64 (phongEvalD).
+template <bool MIX = true>
 __device__ __forceinline__ bool glossyParentEval(const GatherArgs &a, float index, f3 kd, f3 n, f3 wi, f3 wo, float cosWi,
                                                  float cosWo, f3 &f, float &pdf, uint32_t *state = nullptr) {
   const uint32_t bi = (uint32_t)index;
@@ -261,35 +350,8 @@ __device__ __forceinline__ bool glossyParentEval(const GatherArgs &a, float inde
     pdf = w * (INV_FOURPI_F * ia2 * E * frcp(wiH * cH * cH * cH)) + (1.f - w) * (INV_PI_F * cosWo);
     return true;
   }
-  if (kind == GVPM_BSDF_ROUGHCONDUCTOR || kind == GVPM_BSDF_ROUGHCONDUCTOR_ANISO) {
-    const float4 b2 = a.bsdfs[4 * bi + 2], b3 = a.bsdfs[4 * bi + 3];
-    const float alpha = bsdfAlpha(b1);
-    const int dist = bsdfDistribution(b1), vis = bsdfSampleVisible(b1) != 0;
-    f3 H = wi + wo;
-    H = H * frsq(dot(H, H));
-    const float cH = dot(H, n), wiH = dot(wi, H), woH = dot(wo, H);
-    float D, alI = alpha, alO = alpha;  // (anisotropic: alphaU = the head's alpha, the roughness projected on wi and on wo)
-    if (kind == GVPM_BSDF_ROUGHCONDUCTOR) {
-      D = microfacetD(dist, alpha, cH);
-    } else {
-      const float4 fr = a.bsdfs[4 * (bi + 1)];
-      f3 s, t;
-      if (!anisoFrame(fr, n, s, t)) return false;
-      D = microfacetDAniso(dist, alpha, bsdfFrameAlphaV(fr), dot(H, s), dot(H, t), cH);
-      if (D != 0.f) {
-        alI = projectRoughness(alpha, bsdfFrameAlphaV(fr), dot(wi, s), dot(wi, t), cosWi);
-        alO = projectRoughness(alpha, bsdfFrameAlphaV(fr), dot(wo, s), dot(wo, t), cosWo);
-      }
-    }
-    if (D == 0.f) return true;  // eval and pdf both zero (pdfAll = D cos_H, pdfVisible = D G1 ...)
-    const float G1i = microfacetG1(dist, alI, cosWi, wiH), G1o = microfacetG1(dist, alO, cosWo, woH);
-    const float model = fdiv(D * G1i * G1o, 4.f * cosWi);
-    f = mk3(fresnelConductor(wiH, bsdfConductorEta<0>(b2), bsdfConductorK<0>(b2, b3)) * bsdfSpecular<0>(b0),
-            fresnelConductor(wiH, bsdfConductorEta<1>(b2), bsdfConductorK<1>(b2, b3)) * bsdfSpecular<1>(b0),
-            fresnelConductor(wiH, bsdfConductorEta<2>(b2), bsdfConductorK<2>(b2, b3)) * bsdfSpecular<2>(b0)) * model;
-    pdf = vis ? fdiv(D * G1i, 4.f * cosWi) : fdiv(D * cH, 4.f * fabsf(woH));
-    return true;
-  }
+  if (kind == GVPM_BSDF_ROUGHCONDUCTOR || kind == GVPM_BSDF_ROUGHCONDUCTOR_ANISO)
+    return roughConductorEval(a, bi, b0, b1, kind, n, wi, wo, cosWi, cosWo, f, pdf);
   if (kind == GVPM_BSDF_ROUGHPLASTIC || kind == GVPM_BSDF_PLASTIC) {
     // src/bsdfs/roughplastic.cpp:326-437,566-586 and the diffuse component of src/bsdfs/plastic.cpp:245-307,451-477
     // (include/gvpm_hip.h): row 2 = {eta, Fdr, -, component met}, row 3 = {nonlinear, ...}; a rough-plastic head is followed by
@@ -336,6 +398,9 @@ __device__ __forceinline__ bool glossyParentEval(const GatherArgs &a, float inde
     f = mk3(r.x, r.y, r.z);
     pdf = r.w;
     return true;
+  }
+  if constexpr (MIX) {
+    if (kind == GVPM_BSDF_MIXTURE) return mixtureEval(a, bi, kd, n, wi, wo, cosWi, cosWo, f, pdf);
   }
   return false;
 }

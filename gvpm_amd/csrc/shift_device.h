@@ -120,7 +120,7 @@ __device__ __forceinline__ PhotonCold loadCold(const GatherArgs &a, uint32_t idx
 // Written branch-free apart from the shadow-ray loop: every early `return false` of the reference
 // (shift_volume_photon.cpp:398-412, shift_diffuse.cpp:43-47, 100-104, :463-470) clears `good`, the
 // arithmetic runs for all lanes and the result is selected at the end.
-template <bool FULLVIS>
+template <bool FULLVIS, bool MIX = true>
 __device__ __forceinline__ float shiftDiffuse(const GatherArgs &a, const PhotonCold &ph,
                                               uint32_t bits, f3 dProjU, const RayReg &sh, const RayReg &base,
                                               uint32_t edge, f3 trShift, float pdfBaseRay, float pdfShiftRay,
@@ -170,7 +170,7 @@ __device__ __forceinline__ float shiftDiffuse(const GatherArgs &a, const PhotonC
   if (isGlossy) {
     // (a branch of its own: scenes without glossy walls pay one wave-uniform test)
     uint32_t gst = 0u;
-    if (!glossyParentEval(a, ph.parentG, ph.parentScat, ph.parentN, ph.parentWi, dProj, cosWi, cosWo, thr, pdfValue, &gst)) good = false;
+    if (!glossyParentEval<MIX>(a, ph.parentG, ph.parentScat, ph.parentN, ph.parentWi, dProj, cosWi, cosWo, thr, pdfValue, &gst)) good = false;
     pdfTiny = (gst & 1u) != 0u;
     if (amb && (gst & 2u)) *amb |= 32u;
   }

@@ -453,8 +453,8 @@ class Context:
     def upload_bsdfs(self, table):
         """table: numpy array of abi.BSDF_DTYPE (the scene's glossy surfaces); a GVPM_BSDF_ROUGHPLASTIC entry is followed by the
         7 raw entries of its transmittance slice (abi.rtrans_entries), a GVPM_BSDF_WARD_ANISO / GVPM_BSDF_ROUGHCONDUCTOR_ANISO
-        entry by its frame entry (abi.aniso_entry); abi.bsdf_heads tells the heads.  A refused table leaves the previous one
-        in force."""
+        entry by its frame entry (abi.aniso_entry); a GVPM_BSDF_MIXTURE entry (abi.mixture_entry) names its two children by
+        table index, anywhere in the table; abi.bsdf_heads tells the heads.  A refused table leaves the previous one in force."""
         table = np.ascontiguousarray(table, abi.BSDF_DTYPE)
         self._check(lib().gvpm_upload_bsdfs(self._h, table.ctypes.data if table.size else None, table.size))
 

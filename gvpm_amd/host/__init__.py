@@ -55,6 +55,9 @@ def lib():
         L.gvpm_synth_sample_conductor.argtypes = L.gvpm_synth_sample_aniso.argtypes
         L.gvpm_synth_sample_dielectric.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gvpm_synth_sample_mixture.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gvpm_synth_mixture.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.gvpm_synth_sensor.argtypes = [C.c_void_p, C.POINTER(abi.Sensor)]
         L.gvpm_synth_jitter.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
         _LIB = L
@@ -172,6 +175,27 @@ class SynthScene:
         if rc < 0:
             raise ValueError(f"sample_dielectric({mat}): not a rough-dielectric material")
         return (wo, weight, pdf.value, comp.value) if rc == 1 else None
+
+    def sample_mixture(self, mat, n, wi, u1, u2):
+        """one bounce off mixture material `mat` as the light-path walk takes it, component selection included: (wo, weight, pdf,
+        component, sampled type 0x2 | 0x8) or None when the sample is lost; component -1: both children were in play, else the child
+        the vertex was sampled through (pdfComponent is in weight and pdf)"""
+        n, wi = np.ascontiguousarray(n, np.float64), np.ascontiguousarray(wi, np.float64)
+        wo, weight = np.zeros(3), np.zeros(3)
+        pdf, comp, typ = C.c_double(0), C.c_int(0), C.c_int(0)
+        rc = lib().gvpm_synth_sample_mixture(self._h, mat, n.ctypes.data, wi.ctypes.data, u1, u2, wo.ctypes.data, weight.ctypes.data,
+                                             C.addressof(pdf), C.addressof(comp), C.addressof(typ))
+        if rc < 0:
+            raise ValueError(f"sample_mixture({mat}): not a mixture material")
+        return (wo, weight, pdf.value, comp.value, typ.value) if rc == 1 else None
+
+    def mixture(self, mat):
+        """(children (2,) material indices, weights (2,), index of the first table entry) of mixture material `mat`"""
+        children, weights = np.zeros(2, np.int32), np.zeros(2, np.float64)
+        rc = lib().gvpm_synth_mixture(self._h, mat, children.ctypes.data, weights.ctypes.data)
+        if rc < 0:
+            raise ValueError(f"mixture({mat}): not a mixture material")
+        return children, weights, rc
 
     def sensor(self):
         """the scene's pinhole sensor (gvpm_sensor) the compact beam sets are decoded with"""

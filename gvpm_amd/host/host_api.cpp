@@ -261,6 +261,47 @@ static void fillBsdf(const gvpm::SynthMat &m, int kind, int component, gvpm_bsdf
   }
 }
 
+int gvpm_synth_sample_mixture(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
+                              double *weight, double *pdf, int *component, int *type) {
+  using namespace gvpm;
+  if (!s || !n || !wi || !wo || !weight || !pdf || !component || !type || mat < 0 || mat >= (int)s->scene.mats.size())
+    return GVPM_ERR_INVALID_ARG;
+  const SynthMat &pm = s->scene.mats[mat];
+  if (pm.kind != MAT_MIXTURE) return GVPM_ERR_INVALID_ARG;
+  V3 o, w;
+  uint32_t comp = 0;
+  int compSel = -1;
+  if (!sampleMixture(s->scene.mats.data(), pm, V3(n[0], n[1], n[2]), V3(wi[0], wi[1], wi[2]), u1, u2, o, w, *pdf, comp, compSel)) return 0;
+  wo[0] = o.x; wo[1] = o.y; wo[2] = o.z;
+  weight[0] = w.x; weight[1] = w.y; weight[2] = w.z;
+  *component = compSel;
+  *type = (int)comp;
+  return 1;
+}
+
+int gvpm_synth_mixture(const gvpm_synth *s, int mat, int32_t *children, double *weights) {
+  if (!s || !children || !weights || mat < 0 || mat >= (int)s->scene.mats.size() || s->scene.mats[mat].kind != gvpm::MAT_MIXTURE)
+    return GVPM_ERR_INVALID_ARG;
+  const gvpm::SynthMat &m = s->scene.mats[mat];
+  for (int c = 0; c < 2; ++c) {
+    children[c] = m.child[c];
+    weights[c] = m.mixW[c];
+  }
+  return m.bsdf;
+}
+
+// One head of mixture `m` (include/gvpm_hip.h): the weights, the component it is met through + 1 (0: both), and for each child the head
+// of its own table entry, or GVPM_MIXTURE_CHILD_DIFFUSE for the Lambertian (its reflectance rides in the records' parent_scat)
+static void fillMixture(const std::vector<gvpm::SynthMat> &mats, const gvpm::SynthMat &m, int component, gvpm_bsdf *b) {
+  b->kind = GVPM_BSDF_MIXTURE;
+  b->distribution = component;
+  for (int c = 0; c < 2; ++c) {
+    const gvpm::SynthMat &cm = mats[m.child[c]];
+    b->specular[c] = (float)m.mixW[c];
+    b->eta[c] = cm.kind == gvpm::MAT_LAMBERT ? (float)GVPM_MIXTURE_CHILD_DIFFUSE : (float)cm.bsdf;
+  }
+}
+
 uint32_t gvpm_synth_bsdfs(const gvpm_synth *s, gvpm_bsdf *out, uint32_t cap) {
   if (!s) return 0;
   uint32_t n = 0;
@@ -273,7 +314,8 @@ uint32_t gvpm_synth_bsdfs(const gvpm_synth *s, gvpm_bsdf *out, uint32_t cap) {
       if (!out || (uint32_t)(m.bsdf + (c + 1) * stride) > cap) continue;
       gvpm_bsdf *b = &out[m.bsdf + c * stride];
       memset(b, 0, stride * sizeof(gvpm_bsdf));
-      fillBsdf(m, kind, entries == 2 ? c + 1 : 0, b);
+      if (kind == GVPM_BSDF_MIXTURE) fillMixture(s->scene.mats, m, entries == 2 ? c + 1 : 0, b);
+      else fillBsdf(m, kind, entries == 2 ? c + 1 : 0, b);
     }
   }
   return n;

@@ -61,6 +61,15 @@ int gvpm_synth_sample_aniso(const gvpm_synth *s, int mat, const double *n, const
  * (0x8 EGlossyReflection, 0x10 EGlossyTransmission); 0 when the sample is lost; GVPM_ERR_INVALID_ARG for another kind of material. */
 int gvpm_synth_sample_dielectric(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double u3,
                                  double *wo, double *weight, double *pdf, int *component);
+/* A TEST HOOK like gvpm_synth_sample_plastic, for the mixture materials (scenes cbox_mixture*; synth_core.h sampleMixture): one bounce
+ * as the light-path walk takes it, component selection included.  Returns 1 and wo, weight, pdf (solid angle, pdfComponent in it),
+ * *component = the child the vertex was sampled through (-1: both were in play), *type = the sampled lobe's type (0x2
+ * EDiffuseReflection, 0x8 EGlossyReflection); 0 when the sample is lost; GVPM_ERR_INVALID_ARG for another kind of material. */
+int gvpm_synth_sample_mixture(const gvpm_synth *s, int mat, const double *n, const double *wi, double u1, double u2, double *wo,
+                              double *weight, double *pdf, int *component, int *type);
+/* the two children (material indices) and weights of mixture material `mat`; returns the index of its first table entry, or
+ * GVPM_ERR_INVALID_ARG for another kind of material */
+int gvpm_synth_mixture(const gvpm_synth *s, int mat, int32_t *children, double *weights);
 /* the BSDF table of the scene's glossy walls (a rough-plastic head is followed by the raw entries of its slice, an anisotropic head by its
  * frame entry), in the order the photons' parent_g name them (gvpm_upload_bsdfs);
  * returns the number of entries (at most cap are written) */

@@ -370,6 +370,52 @@ bool makeScene(const std::string &fullName, int width, int height, uint32_t seed
     s.addQuad(P(-1, -1), P(-1, 1), P(1, 1), P(1, -1), mPane);  // n = up
     setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);
     setMedium(s, 0.5, 0.5, 0.0);
+  } else if (name == "cbox_mixture" || name == "cbox_mixture1") {
+    // S-cbox with MIXTURE walls (row f4; src/bsdfs/mixturebsdf.cpp, two children of one component each): the ordinary way to a
+    // glossy-diffuse wall out of single-component plugins.  Materials 4..6 are children only (no triangle of their own), their table
+    // entries the ones the mixtures name: 4 copper, Beckmann (alpha 0.3; `1`: 0.03), 5 aluminium, GGX 0.2, 6 brushed copper, Beckmann
+    // 0.12 x 0.45 along the tangent cbox_conductor_aniso gives its back wall.  cbox_mixture: 7 the floor {white Lambertian, 4} at
+    // 0.6 / 0.4, 8 and 9 the side walls {their own colour, 4} at the same weights, 10 the back wall {5, 6} at 0.5 / 0.5 -- four of the
+    // five walls.  cbox_mixture1: 7 the floor {white Lambertian, 4 at alpha 0.03} at 0.7 / 0.3, always met through ONE child (two
+    // heads), 8 the back wall as above; Lambertian side walls.
+    const bool one = name == "cbox_mixture1";
+    auto conductor = [&](int kind, V3 eta, V3 k, double alphaU, double alphaV, int distribution, V3 tangent) {
+      SynthMat m{kind, V3(0.0), V3(1.0), alphaU, 0.0, 0};
+      m.eta = eta;
+      m.k = k;
+      m.distribution = distribution;
+      if (kind == MAT_ROUGHCONDUCTOR_ANISO) {
+        m.alphaV = alphaV;
+        m.tangent = s.toWorld(normalize(tangent));
+      }
+      m.bsdf = 0;
+      for (const auto &q : s.mats) m.bsdf += bsdfSlots(q.kind, q.exponent);
+      s.mats.push_back(m);
+      return (int)s.mats.size() - 1;
+    };
+    auto mixture = [&](int c0, int c1, double w0, double w1) {
+      // (the weights sum to 1: the constructor's rescale, mixturebsdf.cpp:130-142, leaves them)
+      const SynthMat &a0 = s.mats[c0], &a1 = s.mats[c1];
+      SynthMat m{MAT_MIXTURE, a0.kind == MAT_LAMBERT ? a0.albedo : (a1.kind == MAT_LAMBERT ? a1.albedo : V3(0.0)), V3(0.0),
+                 std::fmin(mixtureChildRoughness(a0), mixtureChildRoughness(a1)), 0.0, 0};
+      m.child[0] = c0; m.child[1] = c1;
+      m.mixW[0] = w0; m.mixW[1] = w1;
+      m.bsdf = 0;
+      for (const auto &q : s.mats) m.bsdf += bsdfSlots(q.kind, q.exponent);
+      s.mats.push_back(m);
+      return (int)s.mats.size() - 1;
+    };
+    const V3 cuEta(0.2004, 0.9240, 1.1022), cuK(3.9129, 2.4528, 2.1421);
+    const int cCu = conductor(MAT_ROUGHCONDUCTOR, cuEta, cuK, one ? 0.03 : 0.3, 0.0, GVPM_MICROFACET_BECKMANN, V3(0.0));
+    const int cAl = conductor(MAT_ROUGHCONDUCTOR, V3(1.6574, 0.8803, 0.5212), V3(9.2238, 6.2695, 4.8370), 0.2, 0.0, GVPM_MICROFACET_GGX, V3(0.0));
+    const int cBrushed = conductor(MAT_ROUGHCONDUCTOR_ANISO, cuEta, cuK, 0.12, 0.45, GVPM_MICROFACET_BECKMANN, V3(0.9, 0.35, 0.25));
+    const int mFloor = one ? mixture(0, cCu, 0.7, 0.3) : mixture(0, cCu, 0.6, 0.4);
+    const int mLeft = one ? 1 : mixture(1, cCu, 0.6, 0.4), mRight = one ? 2 : mixture(2, cCu, 0.6, 0.4);
+    const int mBack = mixture(cAl, cBrushed, 0.5, 0.5);
+    addBoxRoom(s, mFloor, 0, mBack, mLeft, mRight, 3);
+    if (rot) addCornellBlocks(s, 0, 0);  // (white blocks: the anisotropic child sits on ONE plane)
+    setLight(s, V3(0, 0.998, 0), 0.5, 0.5, V3(15, 15, 15), 0);
+    setMedium(s, 0.5, 0.5, 0.0);
   } else if (name == "cbox") {
     addBoxRoom(s, 0, 0, 0, 1, 2, 3);
     if (rot) addCornellBlocks(s, 0, 0);

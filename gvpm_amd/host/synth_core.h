@@ -38,6 +38,11 @@ namespace gvpm {
 // over the index above it), `spec` = the specular reflectance, `k` = the specular transmittance.  Two table entries: bsdf = met
 // from the front, bsdf + 1 = met from the back (include/gvpm_hip.h: one entry per side of incidence).  The single global medium
 // lies on both sides.
+// MAT_MIXTURE: src/bsdfs/mixturebsdf.cpp as the reference has it, TWO children of one component each: `child` = two materials of this
+// scene out of MAT_LAMBERT, MAT_ROUGHCONDUCTOR and MAT_ROUGHCONDUCTOR_ANISO (they need not sit on a triangle of their own), `mixW` =
+// the weights after the constructor's rescale; `albedo` = the Lambertian child's reflectance (what the records carry as parent_scat),
+// `exponent` = the smaller of the children's roughnesses: below 0.05 sampleNext picks ONE child per bounce and the material has a
+// table entry per child (bsdf, bsdf + 1), else one.  Its conductor children have entries of their own, which the mixture's name.
 // The glossy kinds are sampled by the HOST generators only: the device generator's closed set is Lambertian / index-matched /
 // mirror (gvpm_devgen_create refuses the others), and their fp64 pow / atan / log chains cost the device walk a third of its
 // time in registers alone when they were merely compiled in.
@@ -47,14 +52,14 @@ namespace gvpm {
 #define GVPM_SYNTH_GLOSSY 1
 #endif
 enum MatKind { MAT_LAMBERT = 0, MAT_NULL = 1, MAT_MIRROR = 2, MAT_PHONG = 3, MAT_ROUGHCONDUCTOR = 4, MAT_WARD = 5, MAT_ROUGHPLASTIC = 6,
-               MAT_PLASTIC = 7, MAT_WARD_ANISO = 8, MAT_ROUGHCONDUCTOR_ANISO = 9, MAT_ROUGHDIELECTRIC = 10 };
+               MAT_PLASTIC = 7, MAT_WARD_ANISO = 8, MAT_ROUGHCONDUCTOR_ANISO = 9, MAT_ROUGHDIELECTRIC = 10, MAT_MIXTURE = 11 };
 // table entries of a glossy material: PathVertex::sampleNext picks ONE component of a Phong surface below roughness 0.05
 // (vertex.cpp:160-165, Phong::getRoughness = sqrt(2 / (2 + exponent)), phong.cpp:293-300): an entry per component then
 GVPM_HD inline bool phongOneComponent(double exponent) { return sqrt(2.0 / (2.0 + exponent)) < 0.05; }
 // (rough plastic: RoughPlastic::sampleComponent, roughplastic.cpp:532-539 -- alpha against the same constant; smooth plastic:
 // its diffuse component alone, the Dirac one is a specular vertex)
 GVPM_HD inline int bsdfEntries(int kind, double exponent) {
-  if (kind == MAT_ROUGHPLASTIC) return exponent < 0.05 ? 2 : 1;
+  if (kind == MAT_ROUGHPLASTIC || kind == MAT_MIXTURE) return exponent < 0.05 ? 2 : 1;  // (the mixture: MixtureBSDF::sampleComponent, :301-314)
   if (kind == MAT_ROUGHDIELECTRIC) return 2;  // (one per side of incidence, at every roughness: sampleComponent returns -1)
   if (kind == MAT_PLASTIC || kind == MAT_WARD_ANISO || kind == MAT_ROUGHCONDUCTOR_ANISO) return 1;
   return kind == MAT_PHONG ? (phongOneComponent(exponent) ? 2 : 1) : ((kind == MAT_ROUGHCONDUCTOR || kind == MAT_WARD) ? 1 : 0);
@@ -70,6 +75,7 @@ GVPM_HD inline int matBsdfKind(int kind) {
     case MAT_WARD_ANISO: return GVPM_BSDF_WARD_ANISO;
     case MAT_ROUGHCONDUCTOR_ANISO: return GVPM_BSDF_ROUGHCONDUCTOR_ANISO;
     case MAT_ROUGHDIELECTRIC: return GVPM_BSDF_ROUGHDIELECTRIC;
+    case MAT_MIXTURE: return GVPM_BSDF_MIXTURE;
     default: return 0;
   }
 }
@@ -99,6 +105,9 @@ struct SynthMat {
   // the anisotropic kinds: alphaU = exponent, alphaV, and the surface's tangent in world space (a unit vector)
   double alphaV = 0.0;
   V3 tangent = V3(0.0);
+  // the mixture: its two children (material indices) and their weights after the rescale
+  int child[2] = {-1, -1};
+  double mixW[2] = {0.0, 0.0};
 };
 
 // what the generators read of a scene (SynthScene::view(); the device gets the arrays in HBM)
@@ -673,6 +682,92 @@ inline bool samplePlastic(const SynthMat &pm, V3 n, V3 wi, double a, double b, V
     return true;
   }
 }
+
+// ---- the two-component mixture (src/bsdfs/mixturebsdf.cpp) ----
+// getRoughness of a child (diffuse.cpp:167-169, roughconductor.cpp:437-440)
+inline double mixtureChildRoughness(const SynthMat &cm) {
+  if (cm.kind == MAT_ROUGHCONDUCTOR) return cm.exponent;
+  if (cm.kind == MAT_ROUGHCONDUCTOR_ANISO) return 0.5 * (cm.exponent + cm.alphaV);
+  return std::numeric_limits<double>::infinity();
+}
+// BSDF::eval (x cos) and BSDF::pdf of a child towards wo: the Lambertian (diffuse.cpp:110-127) or the rough conductor, either form,
+// without visible normals (roughconductor.cpp:257-319).  cos_i > 0 is the caller's.  False: an anisotropic child without a frame.
+inline bool mixtureChildEval(const SynthMat &cm, V3 n, V3 wi, V3 wo, V3 &f, double &pdf) {
+  const double cosWi = dot(n, wi), cosWo = dot(n, wo);
+  f = V3(0.0);
+  pdf = 0.0;
+  if (cosWo <= 0) return true;
+  if (cm.kind == MAT_LAMBERT) {
+    f = cm.albedo * (kInvPi * cosWo);
+    pdf = kInvPi * cosWo;
+    return true;
+  }
+  const V3 H = normalize(wi + wo);
+  const double cH = dot(n, H), wiH = dot(wi, H), woH = dot(wo, H);
+  const int dist = cm.distribution;
+  double D, alI = cm.exponent, alO = cm.exponent;
+  if (cm.kind == MAT_ROUGHCONDUCTOR) {
+    D = conductorD(dist, cm.exponent, cH);
+  } else {
+    V3 sp = cm.tangent - n * dot(n, cm.tangent);
+    if (dot(sp, sp) < 1e-12) return false;
+    sp = normalize(sp);
+    const V3 tp = cross(n, sp);
+    D = conductorDAniso(dist, cm.exponent, cm.alphaV, dot(H, sp), dot(H, tp), cH);
+    alI = projectedAlpha(cm.exponent, cm.alphaV, dot(wi, sp), dot(wi, tp), cosWi);
+    alO = projectedAlpha(cm.exponent, cm.alphaV, dot(wo, sp), dot(wo, tp), cosWo);
+  }
+  if (D == 0) return true;
+  const double G = conductorG1(dist, alI, cosWi, wiH) * conductorG1(dist, alO, cosWo, woH), model = D * G / (4.0 * cosWi);
+  f = V3(conductorFresnel(wiH, cm.eta.x, cm.k.x) * cm.spec.x, conductorFresnel(wiH, cm.eta.y, cm.k.y) * cm.spec.y,
+         conductorFresnel(wiH, cm.eta.z, cm.k.z) * cm.spec.z) * model;
+  pdf = D * cH / (4.0 * std::fabs(woH));
+  return true;
+}
+// BSDF::sample(bRec, pdf, sample) of a child; `pdf` stays 0 where the child found no direction at all
+inline bool mixtureChildSample(const SynthMat &cm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
+  pdf = 0.0;
+  if (cm.kind == MAT_ROUGHCONDUCTOR) return sampleConductor(cm, n, wi, a, b, wo, weight, pdf, comp);
+  if (cm.kind == MAT_ROUGHCONDUCTOR_ANISO) return sampleAniso(cm, n, wi, a, b, wo, weight, pdf, comp);
+  const V3 local = cosineHemisphere(a, b);
+  wo = toWorld(n, local);
+  weight = cm.albedo;
+  comp = GVPM_BSDF_DIFFUSE_REFLECTION;
+  if (local.z <= 0) return false;
+  pdf = local.z * kInvPi;
+  return maxc(weight) > 0;
+}
+// One bounce off a mixture as PathVertex::sampleNext does it (vertex.cpp:160-173) over MixtureBSDF (mixturebsdf.cpp): where a child is
+// smoother than 0.05 sampleComponent (:301-314) picks ONE child with sampleReuse(sample.y) -- the number is re-stretched inside the
+// child's interval and goes on to the child --, sample() (:247-283) returns that child's weight times m_weights, and sampleNext
+// divides by pdfComponent = p_c and multiplies the pdf by it.  Else component -1: sampleReuse(sample.x) picks the child that is
+// sampled, weight = (w_0 eval_0 + w_1 eval_1) / (p_0 pdf_0 + p_1 pdf_1) with the sampled child's eval = its weight times its pdf.
+// No random number beyond the vertex's two.  `mats`: the scene's materials (the children).  False: the sample is lost.
+inline bool sampleMixture(const SynthMat *mats, const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf,
+                          uint32_t &comp, int &compSel) {
+  const double w[2] = {pm.mixW[0], pm.mixW[1]}, p[2] = {w[0] / (w[0] + w[1]), w[1] / (w[0] + w[1])};
+  const SynthMat *ch[2] = {&mats[pm.child[0]], &mats[pm.child[1]]};
+  compSel = -1;
+  if (mixtureChildRoughness(*ch[0]) < 0.05 || mixtureChildRoughness(*ch[1]) < 0.05) {
+    compSel = b < p[0] ? 0 : 1;
+    b = compSel == 0 ? b / p[0] : (b - p[0]) / p[1];
+    if (!mixtureChildSample(*ch[compSel], n, wi, a, b, wo, weight, pdf, comp)) return false;
+    weight = weight * (w[compSel] / p[compSel]);
+    pdf *= p[compSel];
+    return maxc(weight) > 0 && pdf > 0;
+  }
+  const int e = a < p[0] ? 0 : 1, o = 1 - e;
+  a = e == 0 ? a / p[0] : (a - p[0]) / p[1];
+  V3 wgt(0.0), fo;
+  double pe = 0.0, po;
+  // (`temporaryPdf <= 0`: sampling failed; a direction with a pdf and a zero value still counts, the other child is added to it)
+  if (!mixtureChildSample(*ch[e], n, wi, a, b, wo, wgt, pe, comp) && !(pe > 0)) return false;
+  if (!(maxc(wgt) > 0)) wgt = V3(0.0);
+  if (!mixtureChildEval(*ch[o], n, wi, wo, fo, po)) return false;
+  pdf = pe * p[e] + po * p[o];
+  weight = (wgt * (w[e] * pe) + fo * w[o]) * (1.0 / pdf);
+  return maxc(weight) > 0 && pdf > 0;
+}
 #endif
 
 // One light path; mirrors Path::randomWalk(scene, sampler, maxDepth, rrDepth, EImportance)
@@ -858,6 +953,8 @@ template <class PATH> GVPM_HD inline bool walkStep(const SceneView &sc, Philox &
         // every other scene keeps its streams)
         const double c = rng.next1D();
         if (!sampleDielectric(sc.mats[cur.mat], cur.n, wi, a, b, c, wo, cur.weight, cur.pdf, cur.comp)) return false;
+      } else if (cur.matKind == MAT_MIXTURE) {
+        if (!sampleMixture(sc.mats, sc.mats[cur.mat], cur.n, wi, a, b, wo, cur.weight, cur.pdf, cur.comp, cur.compSel)) return false;
 #endif
       } else {
         V3 local = cosineHemisphere(a, b);
@@ -980,6 +1077,9 @@ GVPM_HD inline bool vertexIsDiffuse(const SceneView &sc, const LVertex &v) {
       if (v.matKind == MAT_ROUGHPLASTIC || (v.matKind == MAT_PLASTIC && v.compSel == 1)) return true;
       if (v.matKind == MAT_WARD_ANISO || v.matKind == MAT_ROUGHCONDUCTOR_ANISO) return true;  // (alphas far above bounceRoughness)
       if (v.matKind == MAT_ROUGHDIELECTRIC) return true;  // (RoughDielectric::getRoughness = alpha, far above it too)
+      // (the mixture: the roughness of the child the vertex was sampled through, child 0's with both -- gvpm_struct.h:57-64 --, which
+      // is infinity or a conductor's alpha: above bounceRoughness for every child the scenes have)
+      if (v.matKind == MAT_MIXTURE) return true;
 #endif
       return v.matKind == MAT_LAMBERT || v.matKind == MAT_PHONG || v.matKind == MAT_ROUGHCONDUCTOR || v.matKind == MAT_WARD;
     case VT_MEDIUM: return !(sc.medium.g > 0.5);
@@ -1053,7 +1153,7 @@ template <class PATH> GVPM_HD inline void fillParent(const SceneView &sc, const 
     r.parentScat = par.albedo;
     r.parentWi = normalize(path[ip - 1].pos - par.pos);
     if (par.matKind == MAT_PHONG || par.matKind == MAT_ROUGHCONDUCTOR || par.matKind == MAT_WARD || par.matKind == MAT_WARD_ANISO ||
-        par.matKind == MAT_ROUGHCONDUCTOR_ANISO) {  // (the anisotropic kinds: bsdf names the HEAD, the frame entry follows it)
+        par.matKind == MAT_ROUGHCONDUCTOR_ANISO || par.matKind == MAT_MIXTURE) {  // (the anisotropic kinds: bsdf names the HEAD, the frame entry follows it; the mixture: a head per child below roughness 0.05)
       ptype = GVPM_PARENT_SURFACE_BSDF;
       r.parentG = (float)(sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 : 0));  // (the entry of the component the vertex was sampled through)
     }
@@ -1140,7 +1240,7 @@ template <class RL> GVPM_HD inline void flattenPath(const SceneView &sc, const L
       r.parentScat = par.albedo;
       r.parentWi = normalize(path[i - 2].pos - par.pos);
       if (par.matKind == MAT_PHONG || par.matKind == MAT_ROUGHCONDUCTOR || par.matKind == MAT_WARD || par.matKind == MAT_WARD_ANISO ||
-        par.matKind == MAT_ROUGHCONDUCTOR_ANISO) {  // (the anisotropic kinds: bsdf names the HEAD, the frame entry follows it)
+        par.matKind == MAT_ROUGHCONDUCTOR_ANISO || par.matKind == MAT_MIXTURE) {  // (the anisotropic kinds: bsdf names the HEAD, the frame entry follows it; the mixture: a head per child below roughness 0.05)
         ptype = GVPM_PARENT_SURFACE_BSDF;
         r.parentG = (float)(sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 : 0));  // (the entry of the component the vertex was sampled through)
         comp = par.comp;  // the sampled lobe's type: EGlossyReflection or EDiffuseReflection (vertex.cpp:178-179)
@@ -1255,7 +1355,7 @@ template <class RL, bool BEAMS> struct StreamPath {
           r.parentScat = par.albedo;
           r.parentWi = normalize(path[i - 2].pos - par.pos);
           if (par.matKind == MAT_PHONG || par.matKind == MAT_ROUGHCONDUCTOR || par.matKind == MAT_WARD || par.matKind == MAT_WARD_ANISO ||
-        par.matKind == MAT_ROUGHCONDUCTOR_ANISO) {  // (the anisotropic kinds: bsdf names the HEAD, the frame entry follows it)
+        par.matKind == MAT_ROUGHCONDUCTOR_ANISO || par.matKind == MAT_MIXTURE) {  // (the anisotropic kinds: bsdf names the HEAD, the frame entry follows it; the mixture: a head per child below roughness 0.05)
             ptype = GVPM_PARENT_SURFACE_BSDF;
             r.parentG = (float)(sc.mats[par.mat].bsdf + (par.compSel == 1 ? 1 : 0));  // (the entry of the component the vertex was sampled through)
             comp = par.comp;

@@ -46,7 +46,7 @@ extern "C" {
 
 #define GVPM_ABI_VERSION 3  /* 2: gvpm_bsdf grew to 64 bytes (rough conductor), round 4; 3: gvpm_devgen_scene carries the
                               sensor's rotation (cam_to_world), round 5.  Table kinds and entry points are ADDITIONS and
-                              do not bump it (GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC, the two _ANISO kinds, GVPM_BSDF_ROUGHDIELECTRIC: same 64-byte gvpm_bsdf) */
+                              do not bump it (GVPM_BSDF_ROUGHPLASTIC, GVPM_BSDF_PLASTIC, the two _ANISO kinds, GVPM_BSDF_ROUGHDIELECTRIC, GVPM_BSDF_MIXTURE: same 64-byte gvpm_bsdf) */
 
 /* ---- status codes --------------------------------------------------------*/
 typedef enum gvpm_status {
@@ -312,10 +312,39 @@ typedef struct gvpm_medium {
  *     is copied (GVPM_ERR_INVALID_ARG): alpha < 1e-4, eta[0] not finite or outside [0.2, 5], a reflectance or transmittance
  *     channel outside [0, 1], a non-zero word where zero is asked, `sample_visible` != 0 with
  *     GVPM_MICROFACET_PHONG; GVPM_ERR_UNSUPPORTED: a distribution that is not Beckmann, GGX or Phong.
+ *   GVPM_BSDF_MIXTURE  src/bsdfs/mixturebsdf.cpp as the reference has it: TWO children of one component each (:144-149, :301-314) --
+ *     the ordinary way to a glossy-diffuse wall out of single-component plugins, or a blend of two metals.  The children that can
+ *     occur are the Lambertian, the rough conductor (isotropic or anisotropic, any distribution) and the smooth conductor (a Dirac
+ *     vertex: nothing reconnects through it); Phong, Ward, the plastics and the rough dielectric have two components and the
+ *     reference refuses them.  With the weights w_0, w_1 (m_weights AFTER the constructor's rescale where ensureEnergyConservation is
+ *     on and they sum above 1, :130-142) and p_i = w_i / (w_0 + w_1) (m_pdf, :171-173):
+ *       component -1, both children of roughness >= 0.05:  eval = w_0 eval_0 + w_1 eval_1,  pdf = p_0 pdf_0 + p_1 pdf_1   :177-209
+ *       component c, picked by sampleNext where a child is smoother than 0.05 (vertex.cpp:160-180):
+ *         eval = w_c eval_c,  pdf * pdfComponent = pdf_c p_c                                                              :316-319
+ *     One 64-byte head, no raw entries behind it: specular[0], specular[1] = w_0, w_1 (specular[2] zero); `distribution` = the sampled
+ *     component + 1 as for the Phong kind (0 both, 1 child 0 alone, 2 child 1 alone: a surface that can be met both ways has one
+ *     head per way); eta[0], eta[1] = the two children; every other word +0.  The device derives p_i from the weights.  A CHILD
+ *     WORD is the table index of a GVPM_BSDF_ROUGHCONDUCTOR or GVPM_BSDF_ROUGHCONDUCTOR_ANISO head, as an integer-valued float (as
+ *     parent_g carries one; anywhere in the table, before or after the mixture, and it may be shared), or
+ *     GVPM_MIXTURE_CHILD_DIFFUSE = -1, the Lambertian (diffuse.cpp:110-127), whose reflectance is the record's parent_scat,
+ *     UNWEIGHTED -- the device applies w --, contributing kd / pi cos(theta_o) and cos(theta_o) / pi, or
+ *     GVPM_MIXTURE_CHILD_ABSENT = -2, a child the device cannot evaluate (the smooth conductor), legal only where `distribution`
+ *     selects the OTHER child.  A conductor child contributes what its own head gives alone (its frame entry, its distribution and
+ *     its form of the pdf included); D = 0 there is a zero contribution and the other child still counts; an anisotropic child
+ *     whose tangent is parallel to the normal fails the whole shift, as alone.  cos(theta_i) <= 0 is a failed shift.  A vertex with
+ *     component -1 is classified by child 0's roughness (gvpm_struct.h:57-64), >= 0.05 then: diffuse at the default bounceRoughness.
+ *     gvpm_upload_bsdfs refuses, before anything is copied (GVPM_ERR_INVALID_ARG): a weight that is negative or not finite,
+ *     w_0 + w_1 <= 0, `distribution` outside 0..2, a child word that is not -1, -2 or a non-negative integer below the table's
+ *     length, a child index that names a raw entry, -2 for a child `distribution` selects or with `distribution` 0, an unused word
+ *     that is not +0; GVPM_ERR_UNSUPPORTED: a child head of any other kind (the two-component kinds, a mixture), and BOTH children
+ *     -1 -- legal in the reference, but the pdf is cos / pi either way: the host folds it into a plain GVPM_PARENT_SURFACE record of
+ *     reflectance w_0 kd_0 + w_1 kd_1.
  *   A record of any OTHER kind with cos(theta_i) <= 0 fails its shift, as ever.
  * A surface parent outside the closed set stays what it was: the host flags the photon's shift type 0 (failed shift).   */
 enum { GVPM_BSDF_PHONG = 1, GVPM_BSDF_ROUGHCONDUCTOR = 2, GVPM_BSDF_WARD = 3, GVPM_BSDF_ROUGHPLASTIC = 4, GVPM_BSDF_PLASTIC = 5,
-       GVPM_BSDF_WARD_ANISO = 6, GVPM_BSDF_ROUGHCONDUCTOR_ANISO = 8, GVPM_BSDF_ROUGHDIELECTRIC = 9 };
+       GVPM_BSDF_WARD_ANISO = 6, GVPM_BSDF_ROUGHCONDUCTOR_ANISO = 8, GVPM_BSDF_ROUGHDIELECTRIC = 9, GVPM_BSDF_MIXTURE = 10 };
+#define GVPM_MIXTURE_CHILD_DIFFUSE (-1) /* a mixture's child word: the Lambertian, reflectance = the record's parent_scat    */
+#define GVPM_MIXTURE_CHILD_ABSENT (-2)  /* a mixture's child word: not evaluable on the device (the smooth conductor)        */
 #define GVPM_ANISO_ENTRIES 1           /* raw table entries behind an anisotropic head (the frame entry)            */
 #define GVPM_RTRANS_KNOTS 100          /* values of a rough-plastic slice                                          */
 #define GVPM_RTRANS_ENTRIES 7          /* raw table entries behind a rough-plastic head (448 bytes)                */
@@ -325,14 +354,16 @@ enum { GVPM_WARD_WARD = 0, GVPM_WARD_DUER = 1, GVPM_WARD_BALANCED = 2 };
 enum { GVPM_MICROFACET_BECKMANN = 0, GVPM_MICROFACET_GGX = 1, GVPM_MICROFACET_PHONG = 3 };
 typedef struct gvpm_bsdf {    /* 64 bytes */
   int32_t kind;               /* GVPM_BSDF_*                                                            */
-  float specular[3];          /* m_specularReflectance (Phong: after ensureEnergyConservation, phong.cpp:86-91) */
+  float specular[3];          /* m_specularReflectance (Phong: after ensureEnergyConservation, phong.cpp:86-91);
+                                 mixture: specular[0], specular[1] = the weights w_0, w_1 after the rescale */
   float exponent;             /* Phong: m_exponent; rough conductor, Ward: alpha (the _ANISO kinds: alphaU) */
   float specular_sampling_weight; /* Phong, Ward: m_specularSamplingWeight, phong.cpp:93-97, ward.cpp:158-162 */
-  int32_t distribution;       /* rough conductor: GVPM_MICROFACET_*; Phong: sampled component + 1 (0 = both) */
+  int32_t distribution;       /* rough conductor: GVPM_MICROFACET_*; Phong, mixture: sampled component + 1 (0 = both) */
   int32_t sample_visible;     /* rough conductor: m_sampleVisible (the pdf's form); Ward: GVPM_WARD_* variant */
   float eta[3], k[3];         /* rough conductor: m_eta, m_k (relative to the exterior, roughconductor.cpp:181-191);
                                  plastics: eta[0] = eta, eta[1] = Fdr, k[0] = component met (0 / 1 / 2), k[1] = nonlinear;
-                                 rough dielectric: eta[0] = relative index seen from wi's side, k = m_specularTransmittance */
+                                 rough dielectric: eta[0] = relative index seen from wi's side, k = m_specularTransmittance;
+                                 mixture: eta[0], eta[1] = the children (a head index, GVPM_MIXTURE_CHILD_DIFFUSE or _ABSENT) */
   float reserved[2];
 } gvpm_bsdf;
 
