@@ -1,6 +1,6 @@
 // Internal to libgvpm_hip.so: the handle behind the C ABI (include/gvpm_hip.h), its device buffers and the launch functions of
-// the kernel files.  Shared by gvpm_api.hip (lifecycle, results, comm), uploads.hip (staging of the per-iteration inputs)
-// and the host-only driver units behind gvpm_gather: gather_drivers.hip (entry, shared helpers, G-Planes, host shifts),
+// the kernel files.  Shared by gvpm_api.hip (lifecycle, results, comm), uploads.hip (staging of the per-iteration inputs;
+// staging.h is what the gather entry sees of it), decode_device.hip (the decoders of the packed inputs) and the host-only driver units behind gvpm_gather: gather_drivers.hip (entry, shared helpers, G-Planes, host shifts),
 // drivers_build.hip (photon grid, beam sort), drivers_bre.hip, drivers_beams.hip and drivers_vpm.hip (drivers.h declares
 // what they share).
 #pragma once
@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <chrono>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "device_types.h"
@@ -164,6 +165,32 @@ template <typename T> struct DevBuf {
   }
 };
 
+// The 14 arrays of a gvpm_photon_soa in the ABI's order (include/gvpm_hip.h), spelled here and nowhere else on the host:
+// f(k, array) for k = 0..13; array k holds photonArrayWords(k) 32-bit words per photon, so a photon is 30 words.
+constexpr int PHOTON_ARRAYS = 14;
+constexpr size_t PHOTON_WORDS = 30;
+static inline size_t photonArrayWords(int k) { return k < 8 ? 3 : 1; }
+template <typename Soa, typename F> static inline void forEachPhotonArray(Soa &s, F &&f) {
+  int k = 0;
+  auto each = [&](auto &...a) { (f(k++, a), ...); };
+  each(s.pos, s.wi, s.flux, s.parent_pos, s.parent_n, s.prefix_w, s.parent_scat, s.parent_wi, s.parent_pdf, s.edge_pdf, s.parent_rr,
+       s.parent_g, s.flags, s.path_id);
+}
+struct PhotonArrayPtrs {
+  const void *p[PHOTON_ARRAYS];
+  explicit PhotonArrayPtrs(const gvpm_photon_soa &s) {
+    forEachPhotonArray(s, [&](int k, const auto *a) { p[k] = a; });
+  }
+};
+// points the arrays of `s` into one block of 30 n words at `base`, in the ABI's order (a staging slot; gvpm_host_alloc_photons)
+static inline void photonArraysInBlock(gvpm_photon_soa &s, const uint32_t *base, uint64_t n) {
+  forEachPhotonArray(s, [&](int k, auto &a) {
+    a = reinterpret_cast<std::remove_reference_t<decltype(a)>>(base);
+    base += (size_t)n * photonArrayWords(k);
+  });
+  s.n = n;
+}
+
 struct RcclApi {
   void *dl = nullptr;
   decltype(&ncclGetUniqueId) getUniqueId = nullptr;
@@ -311,10 +338,11 @@ struct gvpm_context {
   // Host uploads land in a ring of three staging slots per kind, through a copy stream of their own: the copy of
   // step N+1 (or, prefetched, N+2) then runs while the kernels of step N still read theirs.  A slot's `copied` event
   // orders its consumers after the copy, `freed` (rays: read until the evaluation kernel ends) the next copy after them.
+  // The protocol is written once, in uploads.hip (staging.h).  Every slot event is created by gvpm_create.
   struct PhotonSlot {
     DevBuf<uint32_t> raw;   // 30 words per photon: the 8 xyz arrays, the 4 scalars, flags, path_id (the ABI's order)
     gvpm_photon_soa dev;    // device pointers into raw
-    DevBuf<uint32_t> packed;  // a packed upload lands here and is decoded into raw (uploads.hip) by the consuming gather
+    DevBuf<uint32_t> packed;  // a packed upload lands here and is decoded into raw (decode_device.hip) by the consuming gather
     bool needUnpack = false;
     bool linked = false;      // `packed` holds a blob of linked records (gvpm_upload_photons_linked)
     hipEvent_t unpacked = nullptr;
@@ -323,7 +351,7 @@ struct gvpm_context {
     // (builds; the G-Planes gather itself): the next copy into the slot waits for both
     hipEvent_t consumed = nullptr, consumedB = nullptr;
     bool read = false;      // a gather has launched kernels that read it since its last copy
-  } phSlot[3];
+  };
   struct RaySlot {
     DevBuf<gvpm_camera_ray> rays;
     DevBuf<uint32_t> packed;  // a packed upload lands here and is decoded into rays by the consuming gather
@@ -334,11 +362,15 @@ struct gvpm_context {
     uint32_t nsets = 0;
     hipEvent_t copied = nullptr, freed = nullptr;
     bool read = false;      // a gather has launched kernels that read it since its last copy
-  } raySlot[3];
-  int phCur = 0, phPending = -1, rayCur = 0, rayPending = -1;   // pending: prefetched, current after the next gather
-  bool phWait = false, rayWait = false;   // the next gather's streams must wait for the current slot's copy
-  bool raysOwnedCur = false;              // the current camera rays live in raySlot[rayCur]
-  bool photonsOwnedCur = false;           // the current photon map lives in phSlot[phCur]
+  };
+  template <typename Slot> struct StagingRing {
+    Slot slot[3];
+    int cur = 0, pending = -1;  // pending: prefetched, current after the next gather
+    bool wait = false;          // the next gather's streams must wait for the current slot's copy
+    bool ownedCur = false;      // the current input lives in slot[cur] (not in borrowed device memory)
+  };
+  StagingRing<PhotonSlot> ph;
+  StagingRing<RaySlot> ray;
   hipStream_t copyStream = nullptr;
   // manifold shifts through the host (gvpm_enable_host_shifts): the requests of the last G-BRE gather
   uint64_t reqCap = 0;

@@ -3,6 +3,7 @@
 // The other techniques' steps are drivers_bre.hip, drivers_beams.hip and drivers_vpm.hip, their builds drivers_build.hip.
 // Mirrors GPMIntegrator::photonMapPass and the computeVolumeGradient* drivers (gvpm/gvpm.cpp:383-500, 880-1180).
 #include "drivers.h"
+#include "staging.h"
 
 float currentRadius(const gvpm_context *h) {
   // breInitSize = bsphere.radius * globalScaleVolume * POURCENTAGE_BS, gvpm.cpp:989 (Float = float)
@@ -331,43 +332,7 @@ static int gatherEntry(gvpm_context *h, int it, uint64_t nb_paths, bool primal) 
     }
   }
   hipStream_t us = breTech && h->pipeline ? h->streamB : h->stream, other = us == h->stream ? h->streamB : h->stream;
-  if (h->phWait) {
-    gvpm_context::PhotonSlot &ps = h->phSlot[h->phCur];
-    HIP_TRY(h, hipStreamWaitEvent(h->stream, ps.copied, 0));
-    HIP_TRY(h, hipStreamWaitEvent(h->streamB, ps.copied, 0));
-    if (ps.needUnpack) {
-      // (a packed record names its parent's material by index: without a table every parent would decode as black)
-      if (h->nmaterials == 0)
-        return fail(h, GVPM_ERR_STATE, "packed photons were uploaded but no material table (gvpm_upload_materials)");
-      if (ps.linked) launch_unpack_linked(ps.packed.p, (uint32_t)ps.dev.n, h->materials.p, h->nmaterials, ps.dev, h->stats.p + 6, us);
-      else launch_unpack_photons(ps.packed.p, (uint32_t)ps.dev.n, h->materials.p, h->nmaterials, ps.dev, h->stats.p + 6, us);
-      HIP_TRY(h, hipGetLastError());
-      if (!ps.unpacked) HIP_TRY(h, hipEventCreateWithFlags(&ps.unpacked, hipEventDisableTiming));
-      HIP_TRY(h, hipEventRecord(ps.unpacked, us));
-      HIP_TRY(h, hipStreamWaitEvent(other, ps.unpacked, 0));
-      ps.needUnpack = false;
-    }
-    h->phWait = false;
-  }
-  if (h->rayWait) {
-    gvpm_context::RaySlot &rs = h->raySlot[h->rayCur];
-    HIP_TRY(h, hipStreamWaitEvent(h->stream, rs.copied, 0));
-    HIP_TRY(h, hipStreamWaitEvent(h->streamB, rs.copied, 0));
-    if (rs.needUnpack) {
-      if (rs.ncompact) {
-        if (!h->haveSensor)
-          return fail(h, GVPM_ERR_STATE, "compact beam sets were uploaded but no sensor (gvpm_upload_sensor)");
-        launch_unpack_compact_rays(h->sensor, rs.compact.p, rs.ncompact, rs.rays.p, us);
-      }
-      launch_unpack_rays(rs.packed.p, rs.nsets - rs.ncompact, rs.rays.p + (size_t)rs.ncompact * 5, us);
-      HIP_TRY(h, hipGetLastError());
-      if (!rs.unpacked) HIP_TRY(h, hipEventCreateWithFlags(&rs.unpacked, hipEventDisableTiming));
-      HIP_TRY(h, hipEventRecord(rs.unpacked, us));
-      HIP_TRY(h, hipStreamWaitEvent(other, rs.unpacked, 0));
-      rs.needUnpack = false;
-    }
-    h->rayWait = false;
-  }
+  if (int rcs = stagingHead(h, us, other)) return rcs;
   h->gatheredPh = h->rawDev;
   h->gatheredPh.n = h->nph;
   h->gatheredRays = h->raysDev;
@@ -384,44 +349,7 @@ static int gatherEntry(gvpm_context *h, int it, uint64_t nb_paths, bool primal) 
     default: return fail(h, GVPM_ERR_UNSUPPORTED, "vol_technique not built in this library yet");
   }
   if (rc != GVPM_OK) return rc;
-  // the kernels just queued on the gather stream are the last readers of this step's camera rays
-  if (h->raysOwnedCur) {
-    HIP_TRY(h, hipEventRecord(h->raySlot[h->rayCur].freed, h->stream));
-    h->raySlot[h->rayCur].read = true;
-  }
-  // ... and of the staged photon arrays (the build on either stream; G-Planes reads them in the gather itself)
-  if (h->photonsOwnedCur) {
-    // G-BRE reads them in its build only (reorder_kernel), and gatherBRE has waited for that build on the host (the
-    // planner's counters): nothing of it is in flight here.  An event behind the whole gather made the prefetched copy
-    // of step N+2 wait for the EVALUATION of step N: the PCIe-inclusive step went from 3.6 to 5.8 ms.  The other
-    // techniques read them on the gather stream (their builds; G-Planes in the gather kernel itself).
-    gvpm_context::PhotonSlot &ps = h->phSlot[h->phCur];
-    const bool bre = h->cfg.vol_technique == GVPM_VOL_BRE2D || h->cfg.vol_technique == GVPM_VOL_BRE3D;
-    if (!bre) {
-      HIP_TRY(h, hipEventRecord(ps.consumed, h->stream));
-      HIP_TRY(h, hipEventRecord(ps.consumedB, h->streamB));
-      ps.read = true;
-    }
-  }
-  // prefetched inputs (gvpm_prefetch_*) become the current ones: what an upload at this point would have done
-  if (h->phPending >= 0) {
-    h->phCur = h->phPending;
-    h->phPending = -1;
-    h->rawDev = h->phSlot[h->phCur].dev;
-    h->nph = (uint32_t)h->rawDev.n;
-    h->phWait = true;
-    h->photonsOwnedCur = true;
-    h->photonsDirty = true;
-  }
-  if (h->rayPending >= 0) {
-    h->rayCur = h->rayPending;
-    h->rayPending = -1;
-    h->raysDev = h->raySlot[h->rayCur].rays.p;
-    h->nsets = h->raySlot[h->rayCur].nsets;
-    h->rayWait = true;
-    h->raysOwnedCur = true;
-    h->beamsDirty = true;
-  }
-  return GVPM_OK;
+  // the kernels just queued are the last readers of the staged inputs; prefetched inputs become the current ones
+  return stagingTail(h);
 }
 }  // extern "C"

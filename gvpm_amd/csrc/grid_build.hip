@@ -186,6 +186,10 @@ struct RawPhotons {
   const float *parent_pdf, *edge_pdf, *parent_rr, *parent_g;
   const uint32_t *flags, *path_id;
 };
+static RawPhotons rawOf(const gvpm_photon_soa &s) {
+  return RawPhotons{s.pos,       s.wi,         s.flux,     s.parent_pos, s.parent_n, s.prefix_w, s.parent_scat,
+                    s.parent_wi, s.parent_pdf, s.edge_pdf, s.parent_rr,  s.parent_g, s.flags,    s.path_id};
+}
 
 __device__ __forceinline__ float4 ld3(const float *p, uint32_t i, float w) {
   return make_float4(p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2], w);
@@ -948,9 +952,7 @@ void launch_beam_near(float4 *cold, uint32_t n, const float4 *tri4, uint32_t ntr
 
 void launch_beam_cold(const gvpm_photon_soa &raw, const float *endN, uint32_t n, const gvpm_params &cfg,
                       const uint32_t *subCounts, float4 *cold, float4 *aux, hipStream_t s) {
-  RawPhotons r{raw.pos,        raw.wi,         raw.flux,     raw.parent_pos, raw.parent_n,
-               raw.prefix_w,   raw.parent_scat, raw.parent_wi, raw.parent_pdf, raw.edge_pdf,
-               raw.parent_rr,  raw.parent_g,   raw.flags,    raw.path_id};
+  const RawPhotons r = rawOf(raw);
   hipLaunchKernelGGL(beam_cold_kernel, dim3((n + 63) / 64), dim3(64), 0, s, r, endN, n, cfg, subCounts, cold, aux);
 }
 
@@ -1050,9 +1052,7 @@ void launch_reorder(const gvpm_photon_soa &raw, const uint32_t *keys, const uint
                     uint32_t n, const gvpm_params &cfg, const float4 *bvh, const float4 *tri4, uint32_t ntri, float dmax,
                     const NearGrid &ng, uint32_t *nearExt, uint32_t extCap, float4 *hot, float4 *cold, uint32_t *overflow,
                     uint32_t *origIdx, const uint32_t *sub, uint32_t ncells, hipStream_t s) {
-  RawPhotons r{raw.pos,        raw.wi,         raw.flux,     raw.parent_pos, raw.parent_n,
-               raw.prefix_w,   raw.parent_scat, raw.parent_wi, raw.parent_pdf, raw.edge_pdf,
-               raw.parent_rr,  raw.parent_g,   raw.flags,    raw.path_id};
+  const RawPhotons r = rawOf(raw);
 #define GVPM_REORDER(M) \
   hipLaunchKernelGGL(reorder_kernel<M>, dim3((n + 63) / 64), dim3(64), 0, s, r, keys, rank, cellStart, n, cfg, bvh, tri4, ntri, \
                      dmax, ng, nearExt, extCap, hot, cold, overflow, origIdx, sub, ncells)
@@ -1490,8 +1490,7 @@ void launch_build_chain(ChainArgs c, const GatherArgs &a, const gvpm_photon_soa 
   t.itemOff = itemOff;
   t.itemCount = c.queueCtl;
   t.blockTotal = c.queueCtl + 3;
-  t.raw = RawPhotons{raw.pos,       raw.wi,          raw.flux,      raw.parent_pos, raw.parent_n, raw.prefix_w, raw.parent_scat,
-                     raw.parent_wi, raw.parent_pdf,  raw.edge_pdf,  raw.parent_rr,  raw.parent_g, raw.flags,    raw.path_id};
+  t.raw = rawOf(raw);
   t.keys = c.keys;
   t.rank = c.rank;
   t.cellStart = c.starts;

@@ -78,14 +78,12 @@ int gvpm_create(const gvpm_params *params, int device, gvpm_context **out) {
     return GVPM_ERR_HIP;
   }
   for (int k = 0; k < 3; ++k)
-    if (hipEventCreateWithFlags(&h->phSlot[k].copied, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->phSlot[k].consumed, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->phSlot[k].consumedB, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->raySlot[k].copied, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->raySlot[k].freed, hipEventDisableTiming) != hipSuccess) {
-      gvpm_destroy(h);
-      return GVPM_ERR_HIP;
-    }
+    for (hipEvent_t *e : {&h->ph.slot[k].copied, &h->ph.slot[k].unpacked, &h->ph.slot[k].consumed, &h->ph.slot[k].consumedB,
+                          &h->ray.slot[k].copied, &h->ray.slot[k].unpacked, &h->ray.slot[k].freed})
+      if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) {
+        gvpm_destroy(h);
+        return GVPM_ERR_HIP;
+      }
   h->bstream = h->stream;
   if (const char *e = getenv("GVPM_BEAMS_PER_WAVE")) {
     int v = atoi(e);
@@ -218,7 +216,7 @@ int gvpm_destroy(gvpm_context *h) {
   if (h->streamA2) (void)hipStreamSynchronize(h->streamA2);
   for (BuildSet &b : h->sets) b.release();
   h->tri4.release(); h->bvh.release();
-  for (auto &ps : h->phSlot) {
+  for (auto &ps : h->ph.slot) {
     ps.raw.release();
     ps.packed.release();
     if (ps.unpacked) (void)hipEventDestroy(ps.unpacked);
@@ -226,9 +224,10 @@ int gvpm_destroy(gvpm_context *h) {
     if (ps.consumed) (void)hipEventDestroy(ps.consumed);
     if (ps.consumedB) (void)hipEventDestroy(ps.consumedB);
   }
-  for (auto &rs : h->raySlot) {
+  for (auto &rs : h->ray.slot) {
     rs.rays.release();
     rs.packed.release();
+    rs.compact.release();
     if (rs.unpacked) (void)hipEventDestroy(rs.unpacked);
     if (rs.copied) (void)hipEventDestroy(rs.copied);
     if (rs.freed) (void)hipEventDestroy(rs.freed);

@@ -1,7 +1,9 @@
 // The packed upload records (include/gvpm_hip.h, "packed uploads"): the decode that DEFINES them, compiled for the host
-// (gvpm_unpack_*) and for the device (unpack kernels, uploads.hip) from this one text.  fp64, no contraction: the two
+// (gvpm_unpack_*, pack_host.hip) and for the device (unpack kernels, decode_device.hip) from this one text.  fp64, no contraction: the two
 // sides produce the same bits.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -77,6 +79,8 @@ GVPM_HD void unpackPhoton(const gvpm_photon_packed &r, const gvpm_material *tabl
 }
 
 // ---- linked photon records (include/gvpm_hip.h) ----
+// a blob's header is the packer's: its limit on n, every offset as the 64-bit layout has it, within `bytes` (pack_host.hip)
+bool linkedHeaderOk(const gvpm_linked_header &hd, size_t bytes);
 GVPM_HD uint32_t linkedKind(const uint32_t *kinds, uint64_t i) { return (kinds[i >> 4] >> (2u * (uint32_t)(i & 15u))) & 3u; }
 // an emit record: everything of the parent but its position and pdfs comes from the blob's emitter table
 GVPM_HD void unpackEmit(const gvpm_photon_emit &r, const gvpm_emitter_entry *emitters, uint32_t n_emitters, const gvpm_photon_soa &d,

@@ -1,5 +1,5 @@
-"""Compact camera-beam sets on the device (gvpm_upload_camera_beams_compact, uploads.hip): the device rebuilds the five rays
-of a sensor-adjacent set exactly as gvpm_unpack_camera_beams_compact does, so a compact upload IS an SoA upload of the
+"""Compact camera-beam sets on the device (gvpm_upload_camera_beams_compact, decode_device.hip): the device rebuilds the five
+rays of a sensor-adjacent set exactly as gvpm_unpack_camera_beams_compact does, so a compact upload IS an SoA upload of the
 unpacked rays -- same counters -- and the oracle fed with the unpacked rays must be matched to the usual bars; against the
 producer's ORIGINAL fp32 rays (whose origins differ in the last bit, see the header) the film stays far inside the bar."""
 import numpy as np

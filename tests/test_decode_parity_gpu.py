@@ -1,4 +1,4 @@
-"""The four device decoders of uploads.hip against the host definitions of the same bytes, BIT FOR BIT, every field:
+"""The four device decoders of decode_device.hip against the host definitions of the same bytes, BIT FOR BIT, every field:
 
     unpack_photons_kernel                          gvpm_unpack_photons
     unpack_linked_kernel + link_linked_kernel      gvpm_unpack_photons_linked

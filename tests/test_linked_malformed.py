@@ -1,5 +1,5 @@
 """Malformed blobs of linked photon records (include/gvpm_hip.h "linked photon records"): what a blob means is DEFINED by
-gvpm_unpack_photons_linked, and the device decoder (uploads.hip) must reject exactly the blobs it rejects.  Here: the host
+gvpm_unpack_photons_linked (pack_host.hip), and the device decoder (decode_device.hip) must reject exactly the blobs it rejects.  Here: the host
 definition refuses hand-edited blobs -- a kind code of 3, per-64-photon group bases that are not the running counts, kinds
 that disagree with the header's counts, a header whose layout only fits uint32 fields by wrapping, a truncated blob -- and a
 sweep of single-bit flips over the kinds and groups words either raises or decodes as the independent numpy decoder does.

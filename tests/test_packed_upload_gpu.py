@@ -1,4 +1,4 @@
-"""Packed uploads on the device (gvpm_upload_*_packed, uploads.hip): the device decodes a record exactly as
+"""Packed uploads on the device (gvpm_upload_*_packed, decode_device.hip): the device decodes a record exactly as
 gvpm_unpack_photons does, so a packed upload is an SoA upload of the unpacked arrays -- same counters, and the oracle fed
 with the unpacked inputs must be matched to the usual bars; against the ORIGINAL inputs the evaluation count is unchanged
 (positions travel as fp32) and the film moves far less than the parity bar."""
