@@ -217,6 +217,7 @@ struct BeamRecPair {
   float pdfBasePos;   // parentPdf * |p1 - p2|^2 [/ |n_end . d|] / v^2
   float trW;          // transmittance of the camera ray up to w (the shifted rays keep w)
   float pdfKernelAndDist;
+  float trOverKernelAndDist;  // the new beam's transmittance over pdfKernelAndDist (beamShift2: from the lengths' difference)
 };
 
 // one reconnection once its new beam p1 -> newPos is known to be unoccluded: nd / dist its direction and length
@@ -262,7 +263,7 @@ __device__ __forceinline__ float reconnectBeamF(const GatherArgs &a, const BeamF
   if (GVPM_PF_EDGE_IN_MEDIUM(b.flags)) {
     const MRecF m = mediumEvalF(a.med, dist);
     sPdf *= m.pdfFailure;
-    thr = thr * fdiv(m.tr, pr.pdfKernelAndDist);
+    thr = thr * (m.tr == 0.f ? 0.f : pr.trOverKernelAndDist);
   }
   if (sPdf == 0.f && !pdfTiny) return 1.f;
   // BeamKernelRecord::kernelPDF of the new beam p1 -> newPos against the shifted ray (shift_volume_beams.h:300-336)
@@ -838,8 +839,30 @@ __device__ __forceinline__ void beamShift2(const GatherArgs &a, LDS &s, const Be
       pr.pdfBasePos = b.parentPdf * (b.len * b.len);
       if (b.endOnSurface) pr.pdfBasePos = fdiv(pr.pdfBasePos, fabsf(dot(b.endN, b.bd)));
       pr.pdfBasePos *= frcp(kV * kV);
-      pr.trW = mediumEvalF(a.med, kW).tr;
+      // Under a thick medium the reconnection's flux is exp(sigma_t (v - dist)) times the base term's scale -- 10^3 at
+      // sigma_t (v - dist) = 7 -- and every rounding of a LENGTH costs sigma_t ulp(length) of it: 1e-6 each for dist, v and w
+      // at sigma_t = 64, one such shift 1e-2 of a frame's mean luminance (tests/test_medium_space_gpu.py, `opaque`).  So
+      // (a) w's optical depth is formed in double from the foot parameter and rounded once, with its remainder;
+      // (b) where pdfFailure is the bare exponential (msw = 1), tr(dist) / pdfFailure(v) = exp(-sigma_t (dist - v)) with
+      //     dist - v = (dist^2 - v^2) / (dist + v) and dist^2 - v^2 = 2 tc (bd.offsetPos - tauV) + |offsetPos|^2 - tauV^2 from
+      //     LOCAL operands (nd = offsetPos + bd tc, v = tc + tauV: tc^2 cancels), good to ~1e-9; pdfKernel is taken back
+      //     out of the queue's product with the same pdfFailure(v) phase 1 multiplied it by.  With msw < 1 pdfFailure is
+      //     bounded below by 1 - msw, nothing is amplified, and the quotient stays as it was.
+      const float sigT = a.med.sigmaT[0];
+      {
+        const double xw = -(double)sigT * (cam.s0 + (double)sigmaW);
+        const float xh = (float)xw;
+        const float eW = expSplit(xh, (float)(xw - (double)xh));
+        pr.trW = eW < 1e-20f ? 0.f : eW;
+      }
       pr.pdfKernelAndDist = q.k.z;
+      if (a.med.msw == 1.f) {
+        const MRecF mV = mediumEvalF(a.med, kV);
+        const float d2 = 2.f * tc * (dot(b.bd, offsetPos) - tauV) + (dot(offsetPos, offsetPos) - tauV * tauV);
+        pr.trOverKernelAndDist = expSplit(-sigT * fdiv(d2, dist + kV), 0.f) * fdiv(mV.pdfFailure, q.k.z);
+      } else {
+        pr.trOverKernelAndDist = fdiv(mediumEvalF(a.med, dist).tr, q.k.z);
+      }
       w = reconnectBeamF(a, b, pr, sh.eye, sh.sMIS, sr, offsetPos, nd, dist, technique, sflux, ok, amb);
     }
 #ifdef GVPM_DBG_SHIFT2  // (probe builds: scripts/probes_py/beams_bisect.py narrows a counter mismatch down to one pair first)

@@ -155,13 +155,19 @@ __device__ __forceinline__ bool evaluatePlane(const GatherArgs &a, const PlaneAr
   const float jBase = (float)fabs(dot(pl.w0, crossd(pl.w1, cam.d)));
   const float invJBase = frcp(jBase);
   const f3 sig2 = mk3(a.med.sigmaS[0] * a.med.sigmaS[0], a.med.sigmaS[1] * a.med.sigmaS[1], a.med.sigmaS[2] * a.med.sigmaS[2]);
-  const f3 baseContrib = sig2 * tof(pl.flux) * (fdiv(mCam.tr * pBase * m1.tr * m0.tr, m0.pdfFailure * m1.pdfFailure) * invJBase);
+  // tr / pdfFailure edge by edge, and 0 behind the 1e-20 cut-off: formed as one quotient, numerator and denominator are
+  // products of up to three exponentials each and leave fp32's range long before their ratio does (sigma_t t > 44 on both
+  // edges: 0 / 0), and behind the cut-off pdfFailure itself underflows where msw = 1 (sigma_t t > 103)
+  const float q0 = m0.tr == 0.f ? 0.f : fdiv(m0.tr, m0.pdfFailure), q1 = m1.tr == 0.f ? 0.f : fdiv(m1.tr, m1.pdfFailure);
+  const f3 baseContrib = sig2 * tof(pl.flux) * (mCam.tr * pBase * (q1 * q0) * invJBase);
   acc[0] += baseContrib.x;
   acc[1] += baseContrib.y;
   acc[2] += baseContrib.z;
   const double w0Dot = dot(pl.w0, pl.w1);
   const double sinW = sqrt(1.0 - w0Dot * w0Dot);
-  const float invM0 = frcp(m0.tr), invM1 = frcp(m1.tr);
+  // (shift_volume_planes.h:346-347 divide by the base transmittances as they are; behind the cut-off baseContrib is 0 and
+  // the shifted flux with it -- the oracle's cutRatio -- where the reference forms 0 * (x / 0))
+  const float invM0 = m0.tr == 0.f ? 0.f : frcp(m0.tr), invM1 = m1.tr == 0.f ? 0.f : frcp(m1.tr);
 #pragma unroll 1
   for (int i = 0; i < 4; ++i) {
     const RayReg sh = loadRay(s, 1 + i, bIdx);
@@ -181,15 +187,16 @@ __device__ __forceinline__ bool evaluatePlane(const GatherArgs &a, const PlaneAr
         const float t0N = (float)t0New, t1N = (float)t1New;
         const MRecP m1s = mediumEvalP(a.med, t1N), m0s = mediumEvalP(a.med, t0N);
         const float jShift = (float)fabs(dot(pl.w0, crossd(newW1, shiftRay.d)));
-        float f = (m0s.tr * invM0) * (m1s.tr * invM1);
-        f = fdiv(f * jBase, jShift);
+        // (each ratio is at most 1e20: they go into the flux one after the other, their product alone may overflow)
+        const float r0 = m0s.tr * invM0, r1 = m1s.tr * invM1;
+        float f = fdiv(jBase, jShift);
         float jac = invJBase * jShift;
         jac = fdiv(jac * t1F, t1N);
         if (pl.edgeID != 1) jac = fdiv(jac * t0F, t0N);
         const float pNew = phaseEval(g, -tof(newW1), -sh.d);
         f = fdiv(f * pNew, pBase);
         w = 0.5f;
-        sflux = baseContrib * (f * jac);
+        sflux = ((baseContrib * r0) * r1) * (f * jac);
         nDiff++;
         if (a.cfg.use_mis) {
           const float basePdf = m0.pdfSuccess * m1.pdfSuccess * pBase;

@@ -361,10 +361,23 @@ int gvpm_upload_medium(gvpm_context *h, const gvpm_medium *m) {
   CHECK_H(h);
   if (int rcj = gvpm_join_exact(h)) return rcj;  // (deferred shifts are evaluated against the scene they met)
   if (!m) return fail(h, GVPM_ERR_INVALID_ARG, "null medium");
+  // (before anything compares them: a NaN sigma_t is a bad argument, not an unsupported medium)
+  bool finite = std::isfinite(m->g) && std::isfinite(m->medium_sampling_weight);
+  for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(m->sigma_a[c]) && std::isfinite(m->sigma_s[c]) && std::isfinite(m->sigma_t[c]);
+  if (!finite) return fail(h, GVPM_ERR_INVALID_ARG, "medium: every field must be finite");
   // homogeneous.cpp:196-200: the balance strategy requires equal sigma_t across channels
   if (m->sigma_t[0] != m->sigma_t[1] || m->sigma_t[0] != m->sigma_t[2])
     return fail(h, GVPM_ERR_UNSUPPORTED, "Not possible to have different albedo values...");
   if (!(m->sigma_t[0] > 0.f)) return fail(h, GVPM_ERR_INVALID_ARG, "sigma_t must be positive");
+  // what the kernels divide by: pdfSuccess = sigma_t e msw (msw = 0), HG's temp = 1 + g^2 + 2 g cos (|g| = 1; hg.cpp refuses
+  // |g| >= 1 too); a scattering coefficient is no negative number and no more than the extinction it is part of
+  if (!(fabsf(m->g) < 1.f)) return fail(h, GVPM_ERR_INVALID_ARG, "medium: the HG mean cosine g must lie in (-1, 1)");
+  if (!(m->medium_sampling_weight > 0.f && m->medium_sampling_weight <= 1.f))
+    return fail(h, GVPM_ERR_INVALID_ARG, "medium: medium_sampling_weight must lie in (0, 1]");
+  for (int c = 0; c < 3; ++c) {
+    if (m->sigma_s[c] < 0.f) return fail(h, GVPM_ERR_INVALID_ARG, "medium: sigma_s must not be negative");
+    if (m->sigma_s[c] > m->sigma_t[c]) return fail(h, GVPM_ERR_INVALID_ARG, "medium: sigma_s must not exceed sigma_t");
+  }
   h->medium = *m;
   h->haveMedium = true;
   return GVPM_OK;

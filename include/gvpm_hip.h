@@ -164,12 +164,19 @@ typedef struct gvpm_params {
 
 /* ---- medium (homogeneous, "balance" strategy) ----------------------------*/
 /* src/medium/homogeneous.cpp:432-513, src/phase/{isotropic,hg}.cpp.          */
+/* gvpm_upload_medium accepts: every field finite; sigma_t equal across the
+ * channels (else GVPM_ERR_UNSUPPORTED) and > 0; 0 <= sigma_s[c] <= sigma_t[c]
+ * (sigma_s may differ per channel); |g| < 1; medium_sampling_weight in (0, 1].
+ * Anything else is GVPM_ERR_INVALID_ARG.  No kernel writes a non-finite value
+ * for an accepted medium, however thick: a transmittance below 1e-20 is 0 as
+ * in the reference, and so is whatever is divided by it.                     */
 typedef struct gvpm_medium {
   float sigma_a[3];
-  float sigma_s[3];
-  float sigma_t[3];             /* must be equal across channels (:196-200)    */
-  float g;                      /* HG mean cosine, 0 = isotropic               */
-  float medium_sampling_weight; /* 1 after computeOnlyVolumeInteraction()      */
+  float sigma_s[3];             /* in [0, sigma_t[c]]                          */
+  float sigma_t[3];             /* must be equal across channels (:196-200), > 0 */
+  float g;                      /* HG mean cosine in (-1, 1), 0 = isotropic    */
+  float medium_sampling_weight; /* in (0, 1]; 1 after
+                                   computeOnlyVolumeInteraction()              */
   float reserved[5];
 } gvpm_medium;
 

@@ -105,6 +105,9 @@ template <typename F> struct PlaneGradRadianceQuery {
     mediumFlux = V((F)0);
   }
 
+  static V cutRatio(const V &a, const V &b) {
+    return a * V(b.x == (F)0 ? (F)0 : (F)1 / b.x, b.y == (F)0 ? (F)0 : (F)1 / b.y, b.z == (F)0 ? (F)0 : (F)1 / b.z);
+  }
   static F invJacobian(const Plane<F> &pl, const V &k) { return (F)(1.0 / std::abs(dot(pl.w0, cross(pl.w1, k)))); }
 
   // getContrib0D, pm/plane_struct.h:150-192
@@ -142,8 +145,12 @@ template <typename F> struct PlaneGradRadianceQuery {
     ctx.medium.eval(Ray<F>(pl.ori, newW1, (F)0, t1New), mRec1Shift);
     ctx.medium.eval(Ray<F>(pl.ori, pl.w0, (F)0, t0New), mRec0Shift);
     V throughputShift = baseContrib;
-    throughputShift *= mRec0Shift.transmittance * V((F)1 / mRec0.transmittance.x, (F)1 / mRec0.transmittance.y, (F)1 / mRec0.transmittance.z);
-    throughputShift *= mRec1Shift.transmittance * V((F)1 / mRec1.transmittance.x, (F)1 / mRec1.transmittance.y, (F)1 / mRec1.transmittance.z);
+    // (:346-347 divide the transmittances as they are.  Medium::eval cuts a transmittance below 1e-20 to 0, and baseContrib
+    // carries both base transmittances as factors: behind the cut the reference forms 0 * (x / 0) = NaN.  A pair whose base
+    // path carries no flux has no shifted flux either: the ratio over a cut transmittance is 0 here, as in
+    // tests/indep_statements.py planes_full and on the device.  Every other pair is as written.)
+    throughputShift *= cutRatio(mRec0Shift.transmittance, mRec0.transmittance);
+    throughputShift *= cutRatio(mRec1Shift.transmittance, mRec1.transmittance);
     throughputShift /= invJacobian(pl, baseCameraRay.d);
     throughputShift *= (F)(1.0 / std::abs(dot(pl.w0, cross(newW1, shiftRay.d))));
     result.jacobian = invJacobian(pl, baseCameraRay.d);

@@ -41,6 +41,11 @@ def run_bre(c, monkeypatch):
                                       ("cbox_rot", dict(vol_technique=abi.GVPM_VOL_BRE2D, use_shift_null=0))])
 def test_every_bre_shift_through_the_exact_pass(scene, kw, monkeypatch):
     c = cases.make_case(scene, 40, 36, 30000, 1.6 if scene.endswith("_rot") else 2.5, **kw)
+    # glossy parents: the table's closed forms are evaluated in fp32 by the pass too (values, not decisions)
+    check_bre(c, monkeypatch, 2e-6 if "phong" not in scene and "conductor" not in scene and "ward" not in scene else 2e-5)
+
+
+def check_bre(c, monkeypatch, bar=2e-6):
     acc, st, taken, lost = run_bre(c, monkeypatch)
     ref, cnt, _ = O.gather_bre(c.p, c.m, c.tris, c.ph, c.rays, c.r, c.it, c.nb, 64, use_accel=False)
     for k in COUNTERS:
@@ -48,13 +53,17 @@ def test_every_bre_shift_through_the_exact_pass(scene, kw, monkeypatch):
     # every shift of every valid shifted ray went through the pass (invalid rays add their weight-1 term in the fast kernel)
     assert lost == 0 and taken >= st["null_shifts"] + st["diffuse_shifts"] + st["failed_shifts"] > 30000
     lum = ref[..., 0:3].mean()
-    # glossy parents: the table's closed forms are evaluated in fp32 by the pass too (values, not decisions)
-    assert l2(acc, ref, lum) < (2e-6 if "phong" not in scene and "conductor" not in scene and "ward" not in scene else 2e-5), l2(acc, ref, lum)
+    assert l2(acc, ref, lum) < bar, l2(acc, ref, lum)
+    return acc, ref, st
 
 
 @pytest.mark.parametrize("scene,kw", [("cbox", dict()), ("cbox_hg", dict(use_mis=0)), ("cbox_rot", dict()), ("fogroom_rot", dict(visibility_as_written=0))])
 def test_every_vpm_shift_through_the_exact_pass(scene, kw, monkeypatch):
     c = make_vpm_case(scene, 32, 28, 40000, 3.1 if scene.endswith("_rot") else 5.0, nb=10, **kw)
+    check_vpm(c, monkeypatch)
+
+
+def check_vpm(c, monkeypatch):
     monkeypatch.setenv("GVPM_EXACT_ALL", "1")
     ctx = hip.Context(c.p, device=0)
     monkeypatch.delenv("GVPM_EXACT_ALL")
@@ -76,6 +85,7 @@ def test_every_vpm_shift_through_the_exact_pass(scene, kw, monkeypatch):
     # (the pass takes the pixel's radius as the fp32 state the device carries: R * 0.01 * scaleVol differs by 1e-7 from the oracle's
     # double product, i.e. 3e-7 in the kernel volume)
     assert l2(acc, ref, lum) < 2e-5, l2(acc, ref, lum)
+    return acc, ref, st
 
 
 @pytest.mark.parametrize("tech", TECHS)
@@ -85,6 +95,10 @@ def test_every_beam_shift_through_the_exact_pass(scene, kw, tech, monkeypatch):
     """G-Beams (gather_beams.hip, exact_beams_kernel): behind the evaluation, every gather; with GVPM_EXACT_ALL every shift of
     every evaluated pair is its to decide and to add -- the fp64 transcription with the shadow segment's triangle tests in fp64."""
     c = make_beam_case(scene, 32, 28, 12000, 1.6 if scene.endswith("_rot") else 2.5, technique=tech, **kw)
+    check_beams(c, monkeypatch)
+
+
+def check_beams(c, monkeypatch):
     monkeypatch.setenv("GVPM_EXACT_ALL", "1")
     ctx = hip.Context(c.p, device=0)
     monkeypatch.delenv("GVPM_EXACT_ALL")
@@ -106,3 +120,4 @@ def test_every_beam_shift_through_the_exact_pass(scene, kw, tech, monkeypatch):
     lum = ref[..., 0:3].mean()
     # (the transcription keeps the reference's float intermediates and rounds every term to float: measured <= 2.2e-5)
     assert l2(acc, ref, lum) < 5e-5, l2(acc, ref, lum)
+    return acc, ref, st

@@ -240,6 +240,53 @@ def test_error_behaviour(case):
     ctx.close()
 
 
+def bad_medium(c, **kw):
+    m = c.sc.medium()
+    for k, v in kw.items():
+        if isinstance(v, tuple):
+            getattr(m, k)[v[0]] = v[1]
+        else:
+            setattr(m, k, v)
+    return m
+
+
+@pytest.mark.parametrize("kw", [
+    dict(g=1.0), dict(g=-1.0), dict(g=1.5), dict(g=float("nan")), dict(g=float("inf")),
+    dict(medium_sampling_weight=0.0), dict(medium_sampling_weight=-0.5), dict(medium_sampling_weight=1.5),
+    dict(medium_sampling_weight=float("nan")),
+    dict(sigma_s=(1, -0.25)), dict(sigma_s=(2, 1.5)), dict(sigma_s=(0, float("nan"))), dict(sigma_s=(1, float("inf"))),
+    dict(sigma_a=(2, float("nan"))), dict(sigma_t=(1, float("nan"))), dict(sigma_t=(0, float("inf"))),
+], ids=lambda kw: "-".join(f"{k}={v}" for k, v in kw.items()).replace(" ", ""))
+def test_upload_medium_refuses_out_of_range_fields(case, kw):
+    """what the kernels divide by (pdfSuccess = sigma_t e msw, HG's 1 + g^2 + 2 g cos) and what no medium is"""
+    ctx = hip.Context(case.p, device=0)
+    try:
+        with pytest.raises(hip.GvpmError) as e:
+            ctx.upload_medium(bad_medium(case, **kw))
+        assert e.value.code == abi.GVPM_ERR_INVALID_ARG, (kw, e.value)
+        assert "medium" in str(e.value)
+        with pytest.raises(hip.GvpmError) as e:      # (a refused medium is not kept)
+            ctx.gather(1, 10)
+        assert e.value.code == abi.GVPM_ERR_STATE
+    finally:
+        ctx.close()
+
+
+def test_upload_medium_accepts_the_trial_media(case):
+    import medium_cases
+    ctx = hip.Context(case.p, device=0)
+    try:
+        for name in medium_cases.MEDIA:
+            c = cases.Case()
+            c.m = case.sc.medium()
+            ctx.upload_medium(medium_cases.apply(c, name).m)
+        ends = bad_medium(case, g=0.999, medium_sampling_weight=1e-3)   # the ends of the ranges; sigma_s = 0 and = sigma_t
+        ends.sigma_s[0], ends.sigma_s[1] = 0.0, ends.sigma_t[1]
+        ctx.upload_medium(ends)
+    finally:
+        ctx.close()
+
+
 def test_full_size_properties():
     """BASELINE configs[1] size (512x512, 1M photons): size-independent properties + a windowed
     oracle comparison of the same frame."""

@@ -38,12 +38,17 @@ def device(c, iters=1, rays=None):
 @pytest.mark.parametrize("scene", ["cbox", "cbox_hg", "cbox_mirror"])
 def test_primal_matches_fp64_oracle(tech, scene):
     c = primal_case(scene, 40, 36, 30000, 2.5, vol_technique=tech, use_shift_null=0)
+    check_primal(c)
+
+
+def check_primal(c):
     acc, st, ref, total = device(c)
     assert st["evaluations"] == total > 10000
     assert st["null_shifts"] == st["diffuse_shifts"] == st["failed_shifts"] == 0
     lum = ref[..., 0:3].mean()
     assert np.sqrt(((acc - ref) ** 2).mean()) / lum < 1e-4
     assert not acc[..., 3:].any()
+    return acc, ref, st
 
 
 def test_three_iterations_radius_schedule_and_max_depth():
