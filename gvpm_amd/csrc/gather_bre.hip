@@ -183,7 +183,10 @@ __device__ __forceinline__ int ownBoxBand(f3 p, f3 o, f3 d, float r, float mint,
   return pass ? 1 : (fail ? 0 : 2);
 }
 
-__device__ __forceinline__ int decidePair(f3 pos, const RayReg &base, float rnd, float r, float eps, bool use3D) {
+// (CFG: the compile-time configuration, shift_device.h -- where it fixes the kernel, the argument is not read)
+template <typename CFG = EvalCfgGeneric>
+__device__ __forceinline__ int decidePair(f3 pos, const RayReg &base, float rnd, float r, float eps, bool use3DCfg) {
+  const bool use3D = cfgFlag<CFG::FIXED, CFG::USE3D>(use3DCfg);
   const float r2f = r * r, mint = eps, maxt = base.len - eps;
   const f3 wv = pos - base.o;
   const float disk = dot(wv, base.d);
@@ -217,7 +220,9 @@ __device__ __forceinline__ int decidePair(f3 pos, const RayReg &base, float rnd,
 // is 4 r E with E the rounding of O(1) coordinate differences, 1e-3 of r^2 -- with the difference vector and the projection
 // formed in fp64, as baseTerms forms them, and the perpendicular offset as a small fp32 vector: d2 to ~4e-7 relative, disk
 // and t' to ~1e-15.  What is still inside THAT band (~1e-6 of the candidates) goes to the exact pass.
-__device__ __forceinline__ int decidePairFine(f3 pos, const RayReg &base, float rnd, float r, float eps, bool use3D) {
+template <typename CFG = EvalCfgGeneric>
+__device__ __forceinline__ int decidePairFine(f3 pos, const RayReg &base, float rnd, float r, float eps, bool use3DCfg) {
+  const bool use3D = cfgFlag<CFG::FIXED, CFG::USE3D>(use3DCfg);
   const d3 wD = tod(pos) - tod(base.o), bdD = tod(base.d);
   const double disk = dot(wD, bdD);
   const f3 perp = tof(wD - bdD * disk);
@@ -261,11 +266,11 @@ struct BaseTerms {
 };
 
 // hit geometry + base contribution of a (photon, beam) pair, shift_volume_photon.cpp:701-751
-template <int B, typename LDS>
+template <int B, typename CFG = EvalCfgGeneric, typename LDS>
 __device__ __forceinline__ BaseTerms baseTerms(const GatherArgs &a, const LDS &s, f3 pos, f3 wi, f3 flux,
                                                const RayReg &base, uint32_t b) {
   BaseTerms t;
-  const bool use3D = a.cfg.vol_technique == GVPM_VOL_BRE3D;
+  const bool use3D = cfgFlag<CFG::FIXED, CFG::USE3D>(a.cfg.vol_technique == GVPM_VOL_BRE3D);
   const float r = a.radius, r2 = r * r;
   // gvpm_accel.h:296-299: disk in fp64, the perpendicular offset as a small vector
   const d3 wD = tod(pos) - tod(base.o), bdD = tod(base.d);
@@ -283,7 +288,7 @@ __device__ __forceinline__ BaseTerms baseTerms(const GatherArgs &a, const LDS &s
     t.pdfCam = frcp(fmaxf(deltaT * 2.f, 0.0001f));
   }
   t.rel = perp + base.d * (float)(disk - t.tPrime);
-  const float rr = a.cfg.path_set ? 2.f : 1.f;
+  const float rr = cfgFlag<CFG::FIXED, CFG::PATH_SET>(a.cfg.path_set) ? 2.f : 1.f;
   t.scale = rr * frcp(kernelVol * t.pdfCam);
   // the base and the four shifted rays all carry mint = Epsilon and maxt = t' (:769-770): one transmittance
   f3 trT;
@@ -303,19 +308,20 @@ __device__ __forceinline__ BaseTerms baseTerms(const GatherArgs &a, const LDS &s
 // against the shifted edge's length within the error band of the fp32 quantities (branchAmbiguous) -- adds nothing and
 // counts nothing here: it is QUEUED like a reconnection, and phase 2, which re-derives the test from the same numbers,
 // hands it to the exact pass (one deferral site in the kernel: its copy loops cost registers).
+template <typename CFG = EvalCfgGeneric>
 __device__ __forceinline__ bool branchAmbiguous(const GatherArgs &a, float y2, float r2, float tPf, float shLen) {
   // y is good to ~2e-7 |y| (the two differences are formed in fp64 / as exact fp32 differences), t' to half an ulp
   // (cfg.reserved[4]: GVPM_EXACT_ALL -- the band widened to everything, so that the exact pass evaluates EVERY shift: a test
   // of the pass against the oracle on whole frames, tests/test_exact_pass_gpu.py)
-  if (a.cfg.reserved[4]) return true;
-  return (a.cfg.use_shift_null && fabsf(y2 - r2) <= 4e-6f * r2) || fabsf(tPf - shLen) <= 4e-7f * (tPf + shLen);
+  if (cfgFlag<CFG::FIXED, CFG::EXACT_ALL>(a.cfg.reserved[4])) return true;
+  return (cfgFlag<CFG::FIXED, CFG::SHIFT_NULL>(a.cfg.use_shift_null) && fabsf(y2 - r2) <= 4e-6f * r2) || fabsf(tPf - shLen) <= 4e-7f * (tPf + shLen);
 }
-template <int B, bool HS, typename LDS>
+template <int B, bool HS, typename CFG = EvalCfgGeneric, typename LDS>
 __device__ __forceinline__ void evalPhase1(const GatherArgs &a, LDS &s, const PhotonFront &ph, const RayReg &base,
                                            uint32_t b, Acc27 &acc, uint32_t &nNull, uint32_t &nFail, uint32_t &qMask) {
   const uint32_t pix = s.pix[b];
   const float r2 = a.radius * a.radius;
-  const BaseTerms bt = baseTerms<B>(a, s, ph.pos, ph.wi, ph.flux, base, b);
+  const BaseTerms bt = baseTerms<B, CFG>(a, s, ph.pos, ph.wi, ph.flux, base, b);
   const f3 bc = bt.bc;
   acc.v[0] += bc.x;
   acc.v[1] += bc.y;
@@ -336,19 +342,20 @@ __device__ __forceinline__ void evalPhase1(const GatherArgs &a, LDS &s, const Ph
     const f3 y = bt.rel - (sh.ro + sh.rd * tPf);
     // shiftNull, shift_volume_photon.cpp:119-158 with the kernel pdfs of :782-801
     const float y2 = dot(y, y);
-    const bool ambBranch = sh.valid && !(HS && st == 3u) && branchAmbiguous(a, y2, r2, tPf, sh.len);
-    const bool isNull = !ambBranch && sh.valid && a.cfg.use_shift_null && y2 < r2 && tPf < sh.len;
+    const bool ambBranch = sh.valid && !(HS && st == 3u) && branchAmbiguous<CFG>(a, y2, r2, tPf, sh.len);
+    const bool isNull = !ambBranch && sh.valid && cfgFlag<CFG::FIXED, CFG::SHIFT_NULL>(a.cfg.use_shift_null) && y2 < r2 && tPf < sh.len;
     const f3 yp = y - sh.d * dot(y, sh.d);
     const float deltaS = fsqrt(fmaxf(0.f, r2 - dot(yp, yp)));
     const float pdfShiftPos = frcp(fmaxf(2.f * deltaS, 0.0001f));
     float wNull = 0.5f;
-    if (a.cfg.use_mis)
+    if (cfgFlag<CFG::FIXED, CFG::USE_MIS>(a.cfg.use_mis))
       wNull = (pdfShiftPos == 0.f || bt.pdfCam == 0.f)
                   ? 1.f
                   : frcp(1.f + sh.sMIS * pdfShiftPos * frcp(bt.pdfCam));
     const f3 nullFlux = photonIn * (bt.tr * phaseEval(a.med.g, ph.wi, -sh.d)) * sh.eye;
     // shiftPhoton dispatch, shift_volume_photon.cpp:49-117: reconnections go to phase 2
-    const bool wantsShift = !ambBranch && sh.valid && !isNull && sh.len >= tPf && a.cfg.debug_shift != GVPM_SHIFT_NULL;
+    const bool wantsShift = !ambBranch && sh.valid && !isNull && sh.len >= tPf &&
+                            !cfgFlag<CFG::FIXED, CFG::DEBUG_SHIFT_NULL>(a.cfg.debug_shift == GVPM_SHIFT_NULL);
     // (a manifold-typed photon goes to phase 2 as well when the host answers such shifts: it records the request there)
     const bool queued = wantsShift && (st == 1u || st == 2u || (HS && st == 3u));
     nNull += isNull ? 1u : 0u;
@@ -441,7 +448,7 @@ void launch_apply_host_shifts(const GatherArgs &a, const gvpm_host_shift *result
 
 // phase 2: one queued reconnection shift (shiftPhotonDiffuse through getShiftPos); the result goes to
 // the lane's registers when it belongs to the lane's current beam, else straight to the LDS accumulators
-template <int B, bool FULLVIS, bool HS, bool MIX, typename LDS>
+template <int B, bool FULLVIS, bool HS, bool MIX, typename CFG = EvalCfgGeneric, typename LDS>
 __device__ __forceinline__ void evalPhase2Core(const GatherArgs &a, LDS &s, uint32_t pidx, uint32_t b, int i, f3 &sf,
                                                f3 &wb, uint32_t &nDiff, uint32_t &nFail, const float4 *ldsTri) {
   const PhotonCold ph = loadCold(a, pidx);
@@ -452,7 +459,8 @@ __device__ __forceinline__ void evalPhase2Core(const GatherArgs &a, LDS &s, uint
   sh.eye = sr.eye;
   sh.len = sr.len;
   sh.valid = sr.valid;
-  const bool use3D = a.cfg.vol_technique == GVPM_VOL_BRE3D;
+  const bool use3D = cfgFlag<CFG::FIXED, CFG::USE3D>(a.cfg.vol_technique == GVPM_VOL_BRE3D);
+  const bool useShiftNull = cfgFlag<CFG::FIXED, CFG::SHIFT_NULL>(a.cfg.use_shift_null);
   const float r = a.radius, r2 = r * r;
   // t', pdfCameraPos and the photon relative to baseRay(t') exactly as phase 1 derived them (baseTerms)
   double tPrime;
@@ -470,7 +478,7 @@ __device__ __forceinline__ void evalPhase2Core(const GatherArgs &a, LDS &s, uint
     }
     rel = perp + base.d * (float)(disk - tPrime);
   }
-  const float rr = a.cfg.path_set ? 2.f : 1.f;
+  const float rr = cfgFlag<CFG::FIXED, CFG::PATH_SET>(a.cfg.path_set) ? 2.f : 1.f;
   const float kernelVol = use3D ? (4.0f / 3.0f) * 3.14159265358979323846f * r2 * r : 3.14159265358979323846f * r2;
   const float scale = rr * frcp(kernelVol * pdfCam);
   f3 trT;
@@ -486,14 +494,15 @@ __device__ __forceinline__ void evalPhase2Core(const GatherArgs &a, LDS &s, uint
   if (!(HS && GVPM_PF_SHIFT_TYPE(ph.bits) == 3u)) {
     const f3 y = rel - dS;
     const float y2 = dot(y, y), tPf = (float)tPrime;
-    amb = branchAmbiguous(a, y2, r2, tPf, sh.len) ? 2u : 0u;
+    amb = branchAmbiguous<CFG>(a, y2, r2, tPf, sh.len) ? 2u : 0u;
     //  Phase 1 queues a shift for two reasons -- it IS a reconnection, or its branch is undecidable -- and
     // tells phase 2 neither: the test above is re-derived from the same numbers.  Should the two sites ever round differently,
     // an entry that is neither here -- not ambiguous, yet a null shift, a photon type without a reconnection, or a shifted edge
     // too short -- was queued as undecidable there: it goes to the exact pass, it is not evaluated as a reconnection.
     const uint32_t stq = GVPM_PF_SHIFT_TYPE(ph.bits);
-    const bool nullNow = a.cfg.use_shift_null && y2 < r2 && tPf < sh.len;
-    const bool reconnects = sh.valid && !nullNow && sh.len >= tPf && a.cfg.debug_shift != GVPM_SHIFT_NULL && (stq == 1u || stq == 2u);
+    const bool nullNow = useShiftNull && y2 < r2 && tPf < sh.len;
+    const bool reconnects = sh.valid && !nullNow && sh.len >= tPf &&
+                            !cfgFlag<CFG::FIXED, CFG::DEBUG_SHIFT_NULL>(a.cfg.debug_shift == GVPM_SHIFT_NULL) && (stq == 1u || stq == 2u);
     if (!amb && !reconnects) amb = 2u;
   }
   // getShiftPos, shift_volume_photon.cpp:858-896: offsetPos = shiftRay(t') + offRel
@@ -504,7 +513,7 @@ __device__ __forceinline__ void evalPhase2Core(const GatherArgs &a, LDS &s, uint
     coherentFrame(sh.d, ns, nt);
     offRel = ns * dot(rel, bs) + nt * dot(rel, bt) + sh.d * dot(rel, base.d);
   }
-  if (a.cfg.use_shift_null) {
+  if (useShiftNull) {
     const f3 bo = dS + offRel;       // offsetPos - baseRay(t')
     const float bo2 = dot(bo, bo);
     // (the mirror decision of getShiftPos moves the offset position by up to 2 r: not a counter, but a different shift)
@@ -539,7 +548,7 @@ __device__ __forceinline__ void evalPhase2Core(const GatherArgs &a, LDS &s, uint
   // 1.4e-4 and two cosine tests at a Phong wall decided differently (found by the `far` transform, tests/test_similarity_gpu.py)
   const f3 dProjU = (((base.o - ph.parentPos) + base.d * (float)tPrime) + dS) + offRel;
   uint32_t ambVis = 0u;
-  float w = shiftDiffuse<FULLVIS, MIX>(a, ph, ph.bits, dProjU, sh, base, s.edge[b], trT, pdfCam, pdfShiftPos, sflux, ok, ldsTri,
+  float w = shiftDiffuse<FULLVIS, MIX, CFG>(a, ph, ph.bits, dProjU, sh, base, s.edge[b], trT, pdfCam, pdfShiftPos, sflux, ok, ldsTri,
                                  sr.sMIS, &ambVis);
   if (amb | ambVis) {
     // fp32 cannot decide this shift as the reference does: the exact pass evaluates it (nothing added, nothing counted)
@@ -1205,6 +1214,17 @@ void launch_traverse_bre(const GatherArgs &a, int beamsPerWave, const uint4 *ite
 #undef GVPM_LAUNCH_TRAV
 }
 
+// The configuration EvalCfgHeadline<!FULLVIS> fixes (shift_device.h), and nothing else: a handle whose gvpm_params differ in any
+// flag the specialised kernel no longer reads runs the generic one, as does GVPM_EVAL_GENERIC=1 (gvpm_api.hip).
+template <bool FULLVIS> static bool headlineConfig(const GatherArgs &a) {
+  using C = EvalCfgHeadline<!FULLVIS>;
+  const auto &c = a.cfg;
+  return !(c.reserved[0] & GVPM_EVAL_FORCE_GENERIC) && (c.vol_technique == GVPM_VOL_BRE3D) == C::USE3D &&
+         (c.use_shift_null != 0) == C::SHIFT_NULL && c.debug_shift == GVPM_SHIFT_ALL && (c.reserved[4] != 0) == C::EXACT_ALL &&
+         (c.path_set != 0) == C::PATH_SET && (c.use_mis != 0) == C::USE_MIS && (c.power_heuristic != 0) == C::POWER_HEURISTIC &&
+         (!C::VIS_FIXED || (c.visibility_as_written != 0) == C::VIS_AS_WRITTEN);
+}
+
 template <bool FULLVIS, bool PF, bool HS = false>
 static void launchEvaluate(const GatherArgs &a, int beamsPerWave, const uint4 *items, const uint2 *itemOff,
                            const uint32_t *itemCount, uint32_t *queueHead, const uint32_t *pairs, const uint32_t *pairCnt,
@@ -1227,7 +1247,23 @@ static void launchEvaluate(const GatherArgs &a, int beamsPerWave, const uint4 *i
   switch (beamsPerWave) {
     case 64: GVPM_LAUNCH_EVAL_B(64); break;
     case 32: GVPM_LAUNCH_EVAL_B(32); break;
-    default: GVPM_LAUNCH_EVAL_B(16); break;
+    default:
+      if constexpr (!PF && !HS) {
+        // the specialised instantiations: B = 16 without the record prefetch and without host shifts
+        if (headlineConfig<FULLVIS>(a)) {
+          using C = EvalCfgHeadline<!FULLVIS>;
+          const dim3 grid((nwaves + SegCfg<16>::WPB - 1) / SegCfg<16>::WPB), block(64 * SegCfg<16>::WPB);
+          if (mix)
+            hipLaunchKernelGGL((evaluate_bre_mix_kernel<16, FULLVIS, false, false, C>), grid, block, dyn, stream, a, items, itemOff, itemCount,
+                               queueHead, pairs, pairCnt, persist, units, unitCtl, unitCap);
+          else
+            hipLaunchKernelGGL((evaluate_bre_kernel<16, FULLVIS, false, false, C>), grid, block, dyn, stream, a, items, itemOff, itemCount,
+                               queueHead, pairs, pairCnt, persist, units, unitCtl, unitCap);
+          break;
+        }
+      }
+      GVPM_LAUNCH_EVAL_B(16);
+      break;
   }
 #undef GVPM_LAUNCH_EVAL_B
 }

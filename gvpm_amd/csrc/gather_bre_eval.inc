@@ -1,7 +1,8 @@
 // The G-BRE evaluation kernel, included by gather_bre.hip once per form: GVPM_EVAL_KERNEL = its name, GVPM_EVAL_MIX = whether it
 // evaluates mixture parents (GVPM_BSDF_MIXTURE; parent_bsdf.h, glossyParentEval<MIX>).  The text is the kernel's own, unchanged: as a
 // __forceinline__ body shared by two __global__ wrappers every instantiation's assembly moved (NOTEBOOK.md, "Mixture parents").
-template <int B, bool FULLVIS, bool PF, bool HS = false>
+// CFG (shift_device.h): EvalCfgGeneric reads the integrator configuration from a.cfg; a fixed one compiles its dead paths out.
+template <int B, bool FULLVIS, bool PF, bool HS = false, typename CFG = EvalCfgGeneric>
 __global__ __launch_bounds__(64 * SegCfg<B>::WPB, GVPM_EVAL_MINW * SegCfg<B>::WPB / 4 > 0 ? GVPM_EVAL_MINW * SegCfg<B>::WPB / 4 : 1) GVPM_EVAL_ATTR
 void GVPM_EVAL_KERNEL(GatherArgs a, const uint4 *__restrict__ items, const uint2 *__restrict__ itemOff,
                              const uint32_t *__restrict__ itemCount, uint32_t *queueHead,
@@ -104,7 +105,7 @@ void GVPM_EVAL_KERNEL(GatherArgs a, const uint4 *__restrict__ items, const uint2
     tk[1] += tMark - tItem;
     tk[6] += 1;
 
-    const bool use3D = a.cfg.vol_technique == GVPM_VOL_BRE3D;
+    const bool use3D = cfgFlag<CFG::FIXED, CFG::USE3D>(a.cfg.vol_technique == GVPM_VOL_BRE3D);
     // my chunk [g0, g1) of the concatenated per-beam lists (lane l of ANY wave position: g0 = min(total, l * chunk))
     const uint32_t chunk = (n + 63u) / 64u;
     const uint32_t g0 = r0 + min(n, (uint32_t)lane * chunk), g1 = min(r0 + n, g0 + chunk);
@@ -172,14 +173,14 @@ void GVPM_EVAL_KERNEL(GatherArgs a, const uint4 *__restrict__ items, const uint2
             l2 = LTICK();
             const PhotonFront ph = PF ? phCur : loadFront(a, pidx);
             const RayReg base = loadRay(s, 0, cur);
-            int dec = decidePair(ph.pos, base, s.rnd[cur], a.radius, a.cfg.epsilon, use3D);
-            if (dec == 2) dec = decidePairFine(ph.pos, base, s.rnd[cur], a.radius, a.cfg.epsilon, use3D);
+            int dec = decidePair<CFG>(ph.pos, base, s.rnd[cur], a.radius, a.cfg.epsilon, use3D);
+            if (dec == 2) dec = decidePairFine<CFG>(ph.pos, base, s.rnd[cur], a.radius, a.cfg.epsilon, use3D);
 #ifdef GVPM_EVAL_TIMING
             asm volatile("" :: "v"(dec));
             l3 = LTICK();
 #endif
             if (dec == 1) {
-              evalPhase1<B, HS>(a, s, ph, base, cur, acc, nNull, nFail, qMask);
+              evalPhase1<B, HS, CFG>(a, s, ph, base, cur, acc, nNull, nFail, qMask);
               dirty = true;
               nEval++;
             } else if (dec == 2) {
@@ -254,7 +255,7 @@ void GVPM_EVAL_KERNEL(GatherArgs a, const uint4 *__restrict__ items, const uint2
           key = k2;
           if (have) {
             f3 sf, wb;
-            evalPhase2Core<B, FULLVIS, HS, GVPM_EVAL_MIX>(a, s, pidx, b, (int)i, sf, wb, nDiff, nFail, ldsTri);
+            evalPhase2Core<B, FULLVIS, HS, GVPM_EVAL_MIX, CFG>(a, s, pidx, b, (int)i, sf, wb, nDiff, nFail, ldsTri);
             rs = rs + sf;
             rw = rw + wb;
           }

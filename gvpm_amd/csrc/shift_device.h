@@ -116,11 +116,36 @@ __device__ __forceinline__ PhotonCold loadCold(const GatherArgs &a, uint32_t idx
   return c;
 }
 
+// A compile-time view of the integrator configuration (gvpm_params: fixed at gvpm_create) for the G-BRE evaluation kernel and the
+// helpers it calls.  FIXED = false: every flag is read from a.cfg where it is used.  FIXED = true: the flags are the constants
+// below and the other side of every test on them is not compiled -- its code counts toward a kernel's register allocation and
+// its uniform compares and selects sit in the hot loops ("Specialised evaluation").
+struct EvalCfgGeneric {
+  static constexpr bool FIXED = false, VIS_FIXED = false;
+  // (not read)
+  static constexpr bool USE3D = false, SHIFT_NULL = false, USE_MIS = false, POWER_HEURISTIC = false, DEBUG_SHIFT_NULL = false,
+                        PATH_SET = false, VIS_AS_WRITTEN = false, EXACT_ALL = false;
+};
+// The configuration of the synthetic hosts' workloads (defaultParams, host/synth.cpp): the 3D kernel with null shifts, MIS with
+// the balance heuristic, the checkerboard path set, no debug filter, no GVPM_EXACT_ALL.  visibility_as_written is fixed (on)
+// where the kernel reads the near lists: the driver starts that form only with it on.  The form that walks the occluder BVH
+// serves both settings -- an overflowing near list sends a handle with it on there -- and keeps the test (VIS = false).
+template <bool VIS> struct EvalCfgHeadline {
+  static constexpr bool FIXED = true, VIS_FIXED = VIS;
+  static constexpr bool USE3D = true, SHIFT_NULL = true, USE_MIS = true, POWER_HEURISTIC = false, DEBUG_SHIFT_NULL = false,
+                        PATH_SET = true, VIS_AS_WRITTEN = true, EXACT_ALL = false;
+};
+// a flag of the configuration: the constant where it is fixed, else what a.cfg says
+template <bool FIXED, bool VALUE> __device__ __forceinline__ constexpr bool cfgFlag(bool fromCfg) {
+  if constexpr (FIXED) return VALUE;
+  else return fromCfg;
+}
+
 // shiftPhotonDiffuse + diffuseReconnection.  Returns the MIS weight, writes the shifted flux.
 // Written branch-free apart from the shadow-ray loop: every early `return false` of the reference
 // (shift_volume_photon.cpp:398-412, shift_diffuse.cpp:43-47, 100-104, :463-470) clears `good`, the
 // arithmetic runs for all lanes and the result is selected at the end.
-template <bool FULLVIS, bool MIX = true>
+template <bool FULLVIS, bool MIX = true, typename CFG = EvalCfgGeneric>
 __device__ __forceinline__ float shiftDiffuse(const GatherArgs &a, const PhotonCold &ph,
                                               uint32_t bits, f3 dProjU, const RayReg &sh, const RayReg &base,
                                               uint32_t edge, f3 trShift, float pdfBaseRay, float pdfShiftRay,
@@ -131,7 +156,7 @@ __device__ __forceinline__ float shiftDiffuse(const GatherArgs &a, const PhotonC
   const float lProj = fsqrt(l2Proj);
   const f3 dProj = dProjU * frcp(lProj);
   const float eps = a.cfg.epsilon, seps = a.cfg.shadow_epsilon;
-  const float vmax = a.cfg.visibility_as_written ? lProj * seps : lProj * (1.f - seps);
+  const float vmax = cfgFlag<CFG::VIS_FIXED, CFG::VIS_AS_WRITTEN>(a.cfg.visibility_as_written) ? lProj * seps : lProj * (1.f - seps);
   // (amb: the caller defers undecidable shifts to the exact pass; without one the plain fp32 decision stands)
   // bit 15 of the record's flags: the parent lies behind a wall it sits on, word 2 of its list is that wall's REACH
   // cstar = |delta| / Epsilon instead of entries (grid_build.hip, ownWall): the wall itself is not listed
@@ -191,13 +216,13 @@ __device__ __forceinline__ float shiftDiffuse(const GatherArgs &a, const PhotonC
   const f3 contrib = sigS * photonWeight * phaseEval(a.med.g, -dProj, -sh.d);
   float w = 0.5f;
   bool misOk = true;
-  if (a.cfg.use_mis) {
+  if (cfgFlag<CFG::FIXED, CFG::USE_MIS>(a.cfg.use_mis)) {
     const float basePdf = pdfBaseRay * ph.parentPdf * ph.edgePdf;
     const float offsetPdf = sPdf * pdfShiftRay;
     misOk = !((offsetPdf == 0.f && !(pdfTiny && pdfShiftRay != 0.f)) || basePdf == 0.f);
     // (sensorMisPre: the caller's per-(shift, beam) value, when it keeps one)
     const float v = (sensorMisPre >= 0.f ? sensorMisPre : sensorMIS(sh, base, edge)) * fdiv(offsetPdf, basePdf);
-    w = a.cfg.power_heuristic ? frcp(1.f + v * v) : frcp(1.f + v);
+    w = cfgFlag<CFG::FIXED, CFG::POWER_HEURISTIC>(a.cfg.power_heuristic) ? frcp(1.f + v * v) : frcp(1.f + v);
   }
   // a failed MIS keeps the flux it computed and takes weight 1 (shift_volume_photon.cpp:463-470)
   shiftedFlux = good ? trShift * contrib * sh.eye : mk3(0.f);  // jacobian == 1
