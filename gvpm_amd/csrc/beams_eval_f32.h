@@ -31,7 +31,7 @@ struct BeamF {
 };
 
 __device__ __forceinline__ BeamF loadBeamF(const GatherArgs &a, uint32_t idx) {
-  // one 128-byte record (grid_build.hip, beam_cold_kernel)
+  // one 128-byte record (beams_build.hip, beam_cold_kernel)
   const float4 *rec = a.cold + (size_t)idx * GVPM_REC_QUADS;
   const float4 c1 = rec[0], c2 = rec[1], c3 = rec[2], c4 = rec[3], c5 = rec[4], c6 = rec[5], c7 = rec[6], c8 = rec[7];
   BeamF b;

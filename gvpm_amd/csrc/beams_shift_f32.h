@@ -99,7 +99,7 @@ constexpr uint32_t SCENE_LDS_TRIS = 128;
 // the local frame.
 //
 // Visibility over the whole new beam [Epsilon, dist] (shift_volume_beams.cpp:420-426): the occluders listed near the
-// beam (beam_near_kernel, grid_build.hip), or all of them when the list overflowed / the scene is large.
+// beam (beam_near_kernel, beams_build.hip), or all of them when the list overflowed / the scene is large.
 // One loop for the lanes that walk their beam's list and the lanes whose list overflowed (every occluder).  In a wave of 64
 // unrelated segments some lane's triangle always passes the plane-side early-out, so every trip (the longest list:
 // 16-19) runs the full Moeller-Trumbore test; marking the crossed planes first and testing only those in a second loop

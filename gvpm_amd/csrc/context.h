@@ -19,41 +19,49 @@
 #include <vector>
 
 #include "device_types.h"
+#include "scan_sort.h"  // scan_sort.hip: sortPairsU32, reserveScanTemp, exclusiveSumU32
 #include "scene_bvh.h"
 
 namespace gvpm {
-hipError_t sortPairsU32(SortTemp &tmp, const uint32_t *kIn, uint32_t *kOut, const uint32_t *vIn, uint32_t *vOut,
-                        uint32_t n, int endBit, hipStream_t s);
+// grid_build.hip: the step-by-step photon grid (launch_sat_z, its pass Z alone, is declared in grid_cells.h for the chain)
 void launch_bounds(const float *pos, uint32_t n, float *partial, int nblocks, float *out6, float *hostOut,
                    hipStream_t s, const uint32_t *word = nullptr, uint32_t *wordOut = nullptr);
-hipError_t reserveScanTemp(SortTemp &tmp, uint32_t n);
-void launch_bundle_fit(const gvpm_camera_ray *rays, uint32_t nsets, int pass, const Grid &g, double *out, hipStream_t s);
 void launch_export_u32(const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, const uint32_t *e, uint32_t *hostOut,
                        hipStream_t s);
-void launch_sat(const uint32_t *cellStart, const Grid &g, uint32_t *sat, hipStream_t s);
 uint32_t cell_stripes();
 void launch_cell_count(const float *pos, uint32_t n, const Grid &g, uint32_t *keys, uint32_t *rank, uint32_t *count, uint32_t *sub,
                        hipStream_t s, uint32_t *zeroWord = nullptr, uint32_t *oneWord = nullptr);
+void launch_sat(const uint32_t *cellStart, const Grid &g, uint32_t *sat, hipStream_t s);
 void launch_reorder(const gvpm_photon_soa &raw, const uint32_t *keys, const uint32_t *rank, const uint32_t *cellStart,
                     uint32_t n, const gvpm_params &cfg, const float4 *bvh, const float4 *tri4, uint32_t ntri, float dmax,
                     const NearGrid &ng, uint32_t *nearExt, uint32_t extCap, float4 *hot, float4 *cold, uint32_t *overflow,
                     uint32_t *origIdx, const uint32_t *sub, uint32_t ncells, hipStream_t s);
-void launch_apply_host_shifts(const GatherArgs &a, const gvpm_host_shift *results, uint32_t n, hipStream_t s);
-// the exact pass over the shifts the evaluation deferred (exact_shift.hip); totals: {evaluated, lost}
-void launch_exact_pass(const GatherArgs &a, unsigned long long *totals, uint32_t *hostOut, hipStream_t s);
-void launch_capture_notes(const GatherArgs &a, hipStream_t s, uint32_t nblocks = 256);
-void launch_exact_beams(const GatherArgs &a, unsigned long long *totals, hipStream_t s);
 void launch_near_grid(const float4 *tri4, uint32_t ntri, const NearGrid &g, float reach, uint32_t *counts, uint32_t *tris, int mode,
                       hipStream_t s);
+void launch_segment_start(const uint32_t *keys, uint32_t n, uint32_t nseg, uint32_t shift, uint32_t *start,
+                          hipStream_t s);
+void launch_bundle_fit(const gvpm_camera_ray *rays, uint32_t nsets, int pass, const Grid &g, double *out, hipStream_t s);
+// beams_build.hip: the camera beams' tile sort, G-Beams' photon-beam records and near lists
+void launch_beam_keys(const gvpm_camera_ray *rays, uint32_t nsets, int width, int tw, int th, uint32_t *keys,
+                      uint32_t *vals, hipStream_t s);
 void launch_beam_count(const gvpm_camera_ray *rays, uint32_t nsets, int width, int tw, int th, uint32_t *keys,
                        uint32_t *rank, uint32_t *count, hipStream_t s);
 void launch_beam_scatter(const uint32_t *keys, const uint32_t *rank, const uint32_t *start, uint32_t n,
                          uint32_t *setPerm, hipStream_t s);
 void launch_tile_start(const uint32_t *start, uint32_t ntiles, uint32_t shift, uint32_t *tileStart, hipStream_t s);
-void launch_segment_start(const uint32_t *keys, uint32_t n, uint32_t nseg, uint32_t shift, uint32_t *start,
-                          hipStream_t s);
-void launch_beam_keys(const gvpm_camera_ray *rays, uint32_t nsets, int width, int tw, int th, uint32_t *keys,
-                      uint32_t *vals, hipStream_t s);
+void launch_beam_cold(const gvpm_photon_soa &raw, const float *endN, uint32_t n, const gvpm_params &cfg,
+                      const uint32_t *subCounts, float4 *cold, float4 *aux, hipStream_t s);
+void launch_shift_extent(const gvpm_camera_ray *rays, uint32_t nsets, uint32_t *extentBits, hipStream_t s);
+void launch_beam_near(float4 *cold, uint32_t n, const float4 *tri4, uint32_t ntri, float r, float eps, const uint32_t *extentBits, float2 *clear, bool freeCone,
+                      hipStream_t s);
+void launch_beam_near_hist(const float4 *cold, uint32_t n, uint32_t ntri, uint32_t *hist, hipStream_t s);
+// build_chain.hip: the G-BRE build (cells, beam sort, summed-volume table, planner, scatter) as one chain of six launches
+void launch_build_chain(ChainArgs c, const GatherArgs &a, const gvpm_photon_soa &raw, int beamsPerWave, uint32_t target, uint4 *items,
+                        uint2 *itemOff, uint32_t itemCap, float dmax, const NearGrid &ng, uint32_t extCap, uint32_t *origIdx,
+                        uint32_t *hostOut, bool initBuckets, hipStream_t s, uint32_t pairCapBlocks = 0xFFFFFFFFu, uint32_t unitCap = 0,
+                        uint32_t unitPairs = 1, bool fullVis = false, bool planGroups = true);
+// gather_bre.hip
+void launch_apply_host_shifts(const GatherArgs &a, const gvpm_host_shift *results, uint32_t n, hipStream_t s);
 void launch_plan_bre(const GatherArgs &a, int beamsPerWave, uint32_t ntiles, uint32_t target, uint4 *items,
                      uint32_t *itemCount, uint2 *itemOff, uint32_t *blockTotal, uint32_t itemCap, hipStream_t stream);
 // units / unitCtl / unitCap: the evaluation's work units (gather_bre.hip, EVAL_UNIT) -- two lists of unitCap entries, their
@@ -63,7 +71,6 @@ void launch_traverse_bre(const GatherArgs &a, int beamsPerWave, const uint4 *ite
                          const uint32_t *itemCount, uint32_t *queueHead, uint32_t *pairs, uint32_t *pairCnt,
                          uint32_t nwaves, bool persistent, hipStream_t stream, uint2 *units = nullptr, uint32_t *unitCtl = nullptr,
                          uint32_t unitCap = 0);
-void launch_apply_host_shifts_beams(const GatherArgs &a, const gvpm_host_shift *results, uint32_t n, hipStream_t s);
 void launch_evaluate_primal(const GatherArgs &a, int beamsPerWave, const uint4 *items, const uint2 *itemOff,
                             const uint32_t *itemCount, uint32_t *queueHead, const uint32_t *pairs, const uint32_t *pairCnt,
                             uint32_t nwaves, hipStream_t stream);
@@ -72,11 +79,53 @@ void launch_evaluate_bre(const GatherArgs &a, int beamsPerWave, bool fullVis, co
                          uint32_t nwaves, bool persistent, hipStream_t stream, const uint2 *units = nullptr,
                          const uint32_t *unitCtl = nullptr, uint32_t unitCap = 0);
 uint32_t plan_items_capacity(uint32_t nsets, uint32_t ntiles, int beamsPerWave);
-// the G-BRE build (cells, beam sort, summed-volume table, planner, scatter) as one chain of six launches (grid_build.hip)
-void launch_build_chain(ChainArgs c, const GatherArgs &a, const gvpm_photon_soa &raw, int beamsPerWave, uint32_t target, uint4 *items,
-                        uint2 *itemOff, uint32_t itemCap, float dmax, const NearGrid &ng, uint32_t extCap, uint32_t *origIdx,
-                        uint32_t *hostOut, bool initBuckets, hipStream_t s, uint32_t pairCapBlocks = 0xFFFFFFFFu, uint32_t unitCap = 0,
-                        uint32_t unitPairs = 1, bool fullVis = false);
+// exact_shift.hip: the exact pass over the shifts the evaluation deferred; totals: {evaluated, lost}
+void launch_exact_pass(const GatherArgs &a, unsigned long long *totals, uint32_t *hostOut, hipStream_t s);
+void launch_capture_notes(const GatherArgs &a, hipStream_t s, uint32_t nblocks = 256);
+// gather_beams.hip
+void launch_apply_host_shifts_beams(const GatherArgs &a, const gvpm_host_shift *results, uint32_t n, hipStream_t s);
+void launch_exact_beams(const GatherArgs &a, unsigned long long *totals, hipStream_t s);
+void launch_beam_subcount(const float *p2, const float *p1, uint32_t n, float ls, uint32_t *counts, uint32_t *maxLs,
+                          hipStream_t s);
+void launch_beam_expand(const float *p2, const float *p1, uint32_t n, const uint32_t *counts, const uint32_t *offsets,
+                        const Grid &g, uint32_t *keys, uint32_t *vals, hipStream_t s);
+void launch_sub_hot(const uint32_t *sortedIds, uint32_t n, const float4 *aux, float4 *hot, uint32_t *hotFlags, hipStream_t s);
+void launch_evaluate_beams(const GatherArgs &a, int beamsPerWave, bool exact, const uint2 *pairs, const uint32_t *sortedKey,
+                           const uint32_t *sortedBlock, uint32_t nBlocks, uint32_t *queueHead, uint32_t nwaves,
+                           hipStream_t stream);
+// gather_beams_trav.hip
+void launch_traverse_beams(const GatherArgs &a, const uint32_t *hotFlags, int beamsPerWave, const uint4 *items,
+                           const uint32_t *itemCount, uint32_t itemCap, uint32_t *queueHead, uint2 *pairs, uint32_t *pairCount,
+                           uint32_t pairCap, uint32_t *blockKey, uint32_t *blockVal, uint32_t nwaves, hipStream_t stream);
+// gather_beams_split.hip
+void launch_evaluate_beams_split(const GatherArgs &a, uint32_t *qId, uint32_t *qMeta, float4 *qK, float *qU, uint32_t *blkCnt,
+                                 uint4 *runTab, uint32_t *ctl, const uint2 *pairs, const uint32_t *sortedKey,
+                                 const uint32_t *sortedBlock, uint32_t nBlocks, uint32_t *queueHead, uint32_t ncu,
+                                 hipStream_t stream);
+// gather_vpm.hip
+void launch_gather_vpm(const GatherArgs &a, bool fullVis, bool primal, hipStream_t stream);
+void launch_vpm_find(const GatherArgs &a, const VpmSplit &sp, hipStream_t stream);
+void launch_vpm_redo(const GatherArgs &a, const VpmSplit &sp, bool fullVis, uint32_t nwaves, hipStream_t stream);
+void launch_vpm_eval(const GatherArgs &a, const VpmSplit &sp, bool fullVis, uint32_t wavesPerShard, hipStream_t stream);
+void launch_vpm_finish(float *accum, float *iter, float *scaleVol, float *nVol, float *mvol, size_t n, float alpha,
+                       uint32_t *maxScaleBits, hipStream_t stream);
+void launch_accumulate(float *accum, float *iter, size_t n, uint32_t *zeroWord, hipStream_t stream);
+// gather_planes.hip
+struct PlaneArgs {
+  const float4 *test;
+  const float *ori, *end, *flux, *w1, *len1;
+  const uint32_t *flags;
+  uint32_t nplanes, planesPerItem;
+};
+void launch_plane_records(const PlaneArgs &pa, float4 *out, hipStream_t stream);
+void launch_gather_planes(const GatherArgs &a, const PlaneArgs &pa, uint32_t ntiles, uint32_t nchunks,
+                          hipStream_t stream);
+// assemble.hip
+void launch_finalize(float *accum, const float *iter, size_t n, int it, uint64_t nbPaths, hipStream_t s);
+void launch_scale(const float *in, float *out, size_t n, float scale, hipStream_t s);
+void launch_film(const float *acc, const float *emission, int w, int h, int it, int reusePrimal, float invDiv,
+                 float *thr, float *dx, float *dy, hipStream_t s);
+// poisson.hip
 struct PoissonGraphCache {
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
@@ -89,48 +138,6 @@ hipError_t poisson_solve_device(const gvpm_poisson_params &prm, int W, int H, co
                                 const float *tp, const float *direct, float *out, void *scratch,
                                 PoissonGraphCache &cache, hipStream_t s);
 size_t poisson_scratch_bytes(int W, int H);
-void launch_finalize(float *accum, const float *iter, size_t n, int it, uint64_t nbPaths, hipStream_t s);
-void launch_scale(const float *in, float *out, size_t n, float scale, hipStream_t s);
-void launch_film(const float *acc, const float *emission, int w, int h, int it, int reusePrimal, float invDiv,
-                 float *thr, float *dx, float *dy, hipStream_t s);
-void launch_gather_vpm(const GatherArgs &a, bool fullVis, bool primal, hipStream_t stream);
-void launch_vpm_find(const GatherArgs &a, const VpmSplit &sp, hipStream_t stream);
-void launch_vpm_redo(const GatherArgs &a, const VpmSplit &sp, bool fullVis, uint32_t nwaves, hipStream_t stream);
-void launch_vpm_eval(const GatherArgs &a, const VpmSplit &sp, bool fullVis, uint32_t wavesPerShard, hipStream_t stream);
-void launch_vpm_finish(float *accum, float *iter, float *scaleVol, float *nVol, float *mvol, size_t n, float alpha,
-                       uint32_t *maxScaleBits, hipStream_t stream);
-void launch_accumulate(float *accum, float *iter, size_t n, uint32_t *zeroWord, hipStream_t stream);
-hipError_t exclusiveSumU32(SortTemp &tmp, const uint32_t *in, uint32_t *out, uint32_t n, hipStream_t s);
-void launch_shift_extent(const gvpm_camera_ray *rays, uint32_t nsets, uint32_t *extentBits, hipStream_t s);
-void launch_beam_near(float4 *cold, uint32_t n, const float4 *tri4, uint32_t ntri, float r, float eps, const uint32_t *extentBits, float2 *clear, bool freeCone,
-                      hipStream_t s);
-void launch_beam_near_hist(const float4 *cold, uint32_t n, uint32_t ntri, uint32_t *hist, hipStream_t s);
-void launch_beam_cold(const gvpm_photon_soa &raw, const float *endN, uint32_t n, const gvpm_params &cfg,
-                      const uint32_t *subCounts, float4 *cold, float4 *aux, hipStream_t s);
-void launch_beam_subcount(const float *p2, const float *p1, uint32_t n, float ls, uint32_t *counts, uint32_t *maxLs,
-                          hipStream_t s);
-void launch_beam_expand(const float *p2, const float *p1, uint32_t n, const uint32_t *counts, const uint32_t *offsets,
-                        const Grid &g, uint32_t *keys, uint32_t *vals, hipStream_t s);
-void launch_sub_hot(const uint32_t *sortedIds, uint32_t n, const float4 *aux, float4 *hot, uint32_t *hotFlags, hipStream_t s);
-void launch_traverse_beams(const GatherArgs &a, const uint32_t *hotFlags, int beamsPerWave, const uint4 *items,
-                           const uint32_t *itemCount, uint32_t itemCap, uint32_t *queueHead, uint2 *pairs, uint32_t *pairCount,
-                           uint32_t pairCap, uint32_t *blockKey, uint32_t *blockVal, uint32_t nwaves, hipStream_t stream);
-void launch_evaluate_beams_split(const GatherArgs &a, uint32_t *qId, uint32_t *qMeta, float4 *qK, float *qU, uint32_t *blkCnt,
-                                 uint4 *runTab, uint32_t *ctl, const uint2 *pairs, const uint32_t *sortedKey,
-                                 const uint32_t *sortedBlock, uint32_t nBlocks, uint32_t *queueHead, uint32_t ncu,
-                                 hipStream_t stream);
-void launch_evaluate_beams(const GatherArgs &a, int beamsPerWave, bool exact, const uint2 *pairs, const uint32_t *sortedKey,
-                           const uint32_t *sortedBlock, uint32_t nBlocks, uint32_t *queueHead, uint32_t nwaves,
-                           hipStream_t stream);
-struct PlaneArgs {
-  const float4 *test;
-  const float *ori, *end, *flux, *w1, *len1;
-  const uint32_t *flags;
-  uint32_t nplanes, planesPerItem;
-};
-void launch_plane_records(const PlaneArgs &pa, float4 *out, hipStream_t stream);
-void launch_gather_planes(const GatherArgs &a, const PlaneArgs &pa, uint32_t ntiles, uint32_t nchunks,
-                          hipStream_t stream);
 }  // namespace gvpm
 
 using namespace gvpm;
@@ -312,6 +319,7 @@ struct gvpm_context {
   Grid bundleGrid{};
   bool buildChain = true;         // G-BRE: the build as one chain of six launches (GVPM_BUILD_CHAIN=0: the separate launches)
   DevBuf<uint32_t> chainCtl;      // its arrival counters
+  bool planGroups = true;         // its planner on the 3D grid walks 64 / B chunks side by side (GVPM_PLAN_GROUPS=0: one at a time)
   bool planBoxHandOff = true;     // G-BRE: the traversal reads the planner's slab boxes (GVPM_PLAN_BOXES=0: computes its own)
   bool beamsFreeCone = true;      // G-Beams: reconnections inside their beam's free cone skip the any-hit loop (GVPM_BEAMS_FREE_CONE=0: none do)
   size_t beamPairsInit = (size_t)16 << 20;  // G-Beams: first capacity of the pair list (GVPM_BEAM_PAIRS_INIT; tests shrink it)
@@ -524,7 +532,7 @@ struct gvpm_context {
   // slots its workgroups, and the next build's kernels, in as others retire)
   bool persistentEval = true, persistentTrav = false;
   // G-BRE: traversal and evaluation are queued behind the build BEFORE the host has read the planner's counters, sized for
-  // what the buffers hold; the build's last block checks (grid_build.hip, TailArgs) and the host queues them again when the
+  // what the buffers hold; the build's last block checks (build_chain.hip, TailArgs) and the host queues them again when the
   // guess was wrong (GVPM_OPTIMISTIC=0: always after the host's wait)
   bool optimistic = true;
   uint32_t lastItems = 0;  // the planner's item count of the last G-BRE step (the traversal's grid of an optimistic step)

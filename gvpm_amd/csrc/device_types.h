@@ -13,10 +13,10 @@ namespace gvpm {
 //     0 {pos, bits} 1 {wi, parentPdf} 2 {flux, edgePdf} 3 {parentPos, parentRR} 4 {parentN, parentG}
 //     5 {prefixW, nearOccluders} 6 {parentScat, -} 7 {parentWi, -}
 // bits = GVPM_PF_* flags of the ABI with bit 7 = pathID & 1.
-// (G-Beams keeps one 128-byte record per BEAM in the same buffer -- grid_build.hip, beam_cold_kernel -- and the sorted
+// (G-Beams keeps one 128-byte record per BEAM in the same buffer -- beams_build.hip, beam_cold_kernel -- and the sorted
 // sub-beam centres in `hot`.)
 #define GVPM_HOT_PARITY_BIT 7
-// per-photon near-occluder lists (grid_build.hip, nearOccluders): 8-bit indices up to NARROW_MAX occluders, 16-bit up
+// per-photon near-occluder lists (near_lists.h, nearOccluders): 8-bit indices up to NARROW_MAX occluders, 16-bit up
 // to WIDE_MAX (the top byte of word 0 must stay below the 0xFD / 0xFE marks), extension lists beyond
 #define GVPM_NEAR_NARROW_MAX 253u
 #define GVPM_NEAR_WIDE_MAX 64767u
@@ -171,7 +171,7 @@ struct GatherArgs {
   uint32_t reqCap;
   const uint32_t *origIdx;  // sorted photon -> index in the upload
   uint32_t *bundleFlag;  // set by the planner when a valid ray is outside the bundle the grid (mode 1) was built for
-  const float2 *beamClear;   // per beam {cosA0, M1}: the free cone of its reconnections (grid_build.hip, beam_near_kernel)
+  const float2 *beamClear;   // per beam {cosA0, M1}: the free cone of its reconnections (beams_build.hip, beam_near_kernel)
   // glossy surface parents (gvpm_upload_bsdfs): 4 float4 per entry {kind, specular} {exponent | alpha, sampling weight,
   // distribution, sample_visible} {eta, k.x} {k.y, k.z, -, -}
   const float4 *bsdfs;
@@ -228,7 +228,7 @@ struct VpmSplit {
   uint32_t *zeroWord;  // cleared by the walk (the largest-scale word)
 };
 
-// The G-BRE build chain (grid_build.hip, launch_build_chain): what its first five launches share.
+// The G-BRE build chain (build_chain.hip, launch_build_chain): what its first five launches share.
 struct ChainArgs {
   // photons -> cells
   const float *pos;
@@ -241,7 +241,7 @@ struct ChainArgs {
   uint32_t scanLen;           // beamOff + nkeys + 1
   uint32_t beamOff;           // ncells + 1
   uint32_t *sub;              // bundle cells: the striped counters (cell_count_kernel), zeroed by the caller
-  uint32_t *buckets;          // 2 x 64 x 6 order-preserving codes: the photons' bounds, the camera beams' (grid_build.hip, ordCode)
+  uint32_t *buckets;          // 2 x 64 x 6 order-preserving codes: the photons' bounds, the camera beams' (build_chain.hip, ordCode)
   float *out6, *hostB6;       // the bounds: device {photons 0-5, beams 6-11}, pinned host {photons 0-5, beams 16-21} (optional)
   // camera-beam sets -> tiles
   const gvpm_camera_ray *rays;

@@ -22,7 +22,7 @@ struct BuildStreamGuard {
   BuildStreamGuard &operator=(const BuildStreamGuard &) = delete;
 };
 
-// G-BRE's build as one chain of launches (grid_build.hip, launch_build_chain): buildGrid / sortBeams then only size the
+// G-BRE's build as one chain of launches (build_chain.hip, launch_build_chain): buildGrid / sortBeams then only size the
 // buffers and the grid and leave here what the chain's launcher needs.
 struct ChainPrep {
   bool on = false;

@@ -13,7 +13,7 @@ void beamTiling(const gvpm_context *h, int beamsPerWave, int &tw, int &th, uint3
   tileShift = ilog2ceil(tw * th) + 3;
 }
 
-// The occluder grid of the near-occluder lists (grid_build.hip: near_grid_kernel, nearVisit): count, scan, fill.  Once per
+// The occluder grid of the near-occluder lists (grid_build.hip: near_grid_kernel; near_lists.h: nearVisit): count, scan, fill.  Once per
 // scene: the one host read-back (the number of entries) stalls nothing that matters.
 static int buildNearGrid(gvpm_context *h, float reach) {
   NearGrid g{};

@@ -637,7 +637,7 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(O
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (the compiler must see it is wave-uniform)
   TravLds &s = sAll[wv];
   const int lane = threadIdx.x & 63;
-  if (itemCount[7] != 0u) return;  // an optimistic step whose buffers were too small (grid_build.hip, TailArgs): queued again
+  if (itemCount[7] != 0u) return;  // an optimistic step whose buffers were too small (build_chain.hip, TailArgs): queued again
   const uint32_t nItems = *itemCount;
   const int b = lane % B, sub = lane / B;
   const float r = a.radius;
@@ -857,7 +857,7 @@ __global__ __launch_bounds__(64 * TRAV_WPB) __attribute__((amdgpu_waves_per_eu(O
                   // own-box test admits diskDistance up to maxt + sqrt(3) r)
                   uint32_t ok = (uint32_t)(d2[e] < thrD2) & (uint32_t)(disk[e] > thrLo) & (uint32_t)(disk[e] < thrHi);
                   // the exact filters, shift_volume_photon.cpp:670-697: computeVolumeContribution + debugShift (bit 6,
-                  // folded by grid_build), checkerboard parity (bit 7), depth window
+                  // folded by reorderBody), checkerboard parity (bit 7), depth window
                   ok &= (uint32_t)((bs[u] & fmask) == fwant);
                   if (depthWindow) ok &= (uint32_t)((uint32_t)((int)GVPM_PF_DEPTH(bs[u]) - dlo) <= dspan);
                   cm |= ok << u;

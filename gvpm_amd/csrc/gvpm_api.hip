@@ -139,6 +139,7 @@ int gvpm_create(const gvpm_params *params, int device, gvpm_context **out) {
   if (const char *e = getenv("GVPM_BEAMS_FREE_CONE")) h->beamsFreeCone = atoi(e) != 0;
   if (const char *e = getenv("GVPM_PLAN_BOXES")) h->planBoxHandOff = atoi(e) != 0;
   if (const char *e = getenv("GVPM_BUILD_CHAIN")) h->buildChain = atoi(e) != 0;
+  if (const char *e = getenv("GVPM_PLAN_GROUPS")) h->planGroups = atoi(e) != 0;
   if (const char *e = getenv("GVPM_EVAL_UNITS")) h->evalUnits = atoi(e) != 0;
   if (const char *e = getenv("GVPM_EVAL_GENERIC"))
     if (atoi(e)) h->cfg.reserved[0] |= GVPM_EVAL_FORCE_GENERIC;  // (gather_bre.hip: launchEvaluate)

@@ -21,7 +21,7 @@ namespace gvpm {
 //   TRI_AMB -- fp32 cannot tell.  The caller DEFERS the shift to the exact pass (exact_shift.hip: the reference's
 //   statement in uncontracted fp64), or, where no exact pass exists, takes bit 0: the plain fp32 decision.
 // The systematic case is a segment that STARTS within rounding of the triangle's plane -- a parent that fp32 left behind
-// the wall it sits on (grid_build.hip, ownWall) -- along a grazing direction: the plane distance of the start is pure
+// the wall it sits on (near_lists.h, ownWall) -- along a grazing direction: the plane distance of the start is pure
 // rounding residue and t >= mint is decided by it.  The generic near-threshold cases (a hit within 1e-6 of an edge) go the same way.
 #define GVPM_TRI_MISS 0
 #define GVPM_TRI_HIT 1
@@ -269,7 +269,7 @@ __device__ __forceinline__ int nearListHit(const float4 *tri, uint32_t nl0, uint
   }
   return res;
 }
-// the same for scenes of more than 254 occluders: six 16-bit indices (grid_build.hip, nearOccluders)
+// the same for scenes of more than 254 occluders: six 16-bit indices (near_lists.h, nearOccluders)
 __device__ __forceinline__ int nearListHitWide(const float4 *tri, uint32_t nl0, uint32_t nl1, uint32_t nl2, f3 o, f3 d,
                                                float mint, float maxt) {
   int res = GVPM_TRI_MISS;

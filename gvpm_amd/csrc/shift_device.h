@@ -159,7 +159,7 @@ __device__ __forceinline__ float shiftDiffuse(const GatherArgs &a, const PhotonC
   const float vmax = cfgFlag<CFG::VIS_FIXED, CFG::VIS_AS_WRITTEN>(a.cfg.visibility_as_written) ? lProj * seps : lProj * (1.f - seps);
   // (amb: the caller defers undecidable shifts to the exact pass; without one the plain fp32 decision stands)
   // bit 15 of the record's flags: the parent lies behind a wall it sits on, word 2 of its list is that wall's REACH
-  // cstar = |delta| / Epsilon instead of entries (grid_build.hip, ownWall): the wall itself is not listed
+  // cstar = |delta| / Epsilon instead of entries (near_lists.h, ownWall): the wall itself is not listed
   const bool behind = (bits >> 15) & 1u;
   const float cosWo = dot(ph.parentN, dProj);
   // (a segment that leaves within cstar of grazing meets the own wall's plane at t >= Epsilon: the exact pass decides; 1.2e-3:

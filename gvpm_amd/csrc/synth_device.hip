@@ -17,10 +17,9 @@
 #include "../../include/gvpm_hip.h"
 #include "../host/synth_core.h"
 #include "device_types.h"
+#include "scan_sort.h"
 
 namespace gvpm {
-
-hipError_t exclusiveSumU32(SortTemp &tmp, const uint32_t *in, uint32_t *out, uint32_t n, hipStream_t s);
 
 namespace {
 

@@ -423,7 +423,7 @@ __device__ __forceinline__ uint32_t boxCount(const GatherArgs &a, const CellBox 
 // chunk is a handful of dependent steps instead of one per slab.
 // ------------------------------------------------------------------------------------------
 // The planner's LDS (one wave): handed in by the kernel, so that a kernel with other roles beside the planner's (the tail of
-// the G-BRE build chain, grid_build.hip) can lay them over one another.
+// the G-BRE build chain, build_chain.hip) can lay them over one another.
 // (PLAN_STAGE: the items staged between two flushes, and the most parts a heavy item is split into; 512 in the planner's
 // own kernel, 128 -- 2.5 KB instead of 10 -- where it shares a launch and a CU with everything else: the build chain's tail)
 template <int B, uint32_t PLAN_STAGE = 512> struct PlanLds {

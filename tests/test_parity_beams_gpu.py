@@ -168,7 +168,7 @@ def test_beam_near_list_formats(levels):
 @pytest.mark.parametrize("scene,scale", [("fogroom", 2.5), ("laser", 2.0), ("laser_hg", 2.0)])
 def test_reconnections_among_occluders(tech, scene, scale):
     """Scenes whose new beams ARE blocked (64 boxes standing in the fog; the aperture plate of S-laser): the evaluation
-    skips the any-hit loop for a reconnection inside its beam's free cone (grid_build.hip, beam_near_kernel) and takes
+    skips the any-hit loop for a reconnection inside its beam's free cone (beams_build.hip, beam_near_kernel) and takes
     the others through it -- a cone that certified a blocked beam would turn failed shifts into reconnections."""
     c = make_beam_case(scene, 32, 28, 12000, scale, technique=tech)
     acc, ref, st = device_beams(c)

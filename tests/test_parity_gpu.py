@@ -640,13 +640,14 @@ def test_optimistic_step_refused_by_the_build_is_queued_again(monkeypatch):
     assert l2(acc1, ref, max(ref[..., 0:3].mean(), 1e-30)) < TOL
 
 
-@pytest.mark.parametrize("variant", ["replan", "bre2d", "GVPM_TRAV_STREAM=0", "GVPM_PIPELINE=0", "GVPM_BUILD_CHAIN=0"])
+@pytest.mark.parametrize("variant", ["replan", "bre2d", "GVPM_TRAV_STREAM=0", "GVPM_PIPELINE=0", "GVPM_BUILD_CHAIN=0", "GVPM_PLAN_GROUPS=0"])
 def test_step_variants_that_no_other_test_reaches(variant, monkeypatch):
     """Branches of the G-BRE step (drivers_bre.hip) outside every other test's way, two iterations each against the
     oracle's fold: the same photons, beams and radius again (alpha = 1, nothing uploaded in between), which re-plans the
     built set in place with the planner as its own launch; a second BRE2D step, whose radius took the square-root
     exponent of scaleVolumeAPA; the two-stage pipeline, whose traversal runs on the build
-    stream; everything on the gather stream; and the build as separate launches instead of the chain."""
+    stream; everything on the gather stream; the build as separate launches instead of the chain; and the chain's planner
+    walking one chunk of a tile's beams at a time (planBody in place of planBodyQ, build_chain.hip)."""
     replan, knob = variant == "replan", "=" in variant
     kw = dict(vol_technique=abi.GVPM_VOL_BRE2D, use_shift_null=0) if variant == "bre2d" else {}
     c = cases.make_case("cbox", 24, 20, 8000, 3.0, **kw)

@@ -1,7 +1,7 @@
 """Parity in GENERAL POSITION (round 5).
 
 Every other scene of the suite is axis-aligned: all normals +-x / +-y / +-z, all wall coordinates exactly representable.
-Three device mechanisms are exact only there -- the own-wall rule of the near-occluder lists (grid_build.hip, ownWall),
+Three device mechanisms are exact only there -- the own-wall rule of the near-occluder lists (near_lists.h, ownWall),
 the octahedral normals of the packed upload (pack_codec.h), the local frames of the glossy parents -- and the slab /
 cylinder / plane-side tests never see a general direction.  The `_rot` scenes (gvpm_amd/host/synth.cpp) put room, light and
 sensor under one fixed rotation (Euler 17 / 31 / 47 degrees) and tilt every inner box on its own; the tests below run all

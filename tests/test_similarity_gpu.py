@@ -17,7 +17,7 @@ Outcome: parity at the harnesses' bars for every technique under every transform
 takes 2.4 % of G-BRE 3D's shifts on the rotated fog room under `centimetres` (0.009 % untransformed), 2.3 % of G-VPM's, 70 % of
 G-Beams 3D's ("Away from the unit room").  What the transforms found, fixed where it was: the reconnection vector
 through an fp32 point (gather_bre.hip evalPhase2Core, gather_vpm.hip vpmPhase2: `far`), the free cone's own-wall sliver as a
-constant angle (grid_build.hip beamClearTri: `centimetres`), plain fp32 shadow segments in the literal G-Beams path
+constant angle (beams_build.hip beamClearTri: `centimetres`), plain fp32 shadow segments in the literal G-Beams path
 (gather_beams.hip: `centimetres`).
 """
 import os
