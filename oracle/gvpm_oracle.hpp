@@ -543,7 +543,8 @@ template <typename F> struct VolumeGradientRecord {
     if ((mode & GVPM_SURF2MEDIA) && (mode & GVPM_MEDIA2MEDIA)) {
     } else {
       if (ptype == GVPM_PARENT_MEDIUM && !(mode & GVPM_MEDIA2MEDIA)) return false;
-      if ((ptype == GVPM_PARENT_SURFACE || ptype == GVPM_PARENT_EMITTER) && !(mode & GVPM_SURF2MEDIA)) return false;
+      // (every isSurfaceInteraction() parent: emitters, Lambertian walls and the glossy GVPM_PARENT_SURFACE_BSDF ones)
+      if (ptype != GVPM_PARENT_MEDIUM && !(mode & GVPM_SURF2MEDIA)) return false;
     }
     const int comp = (int)GVPM_PF_PREV_COMPONENT(ph.flags);
     return !(ctx.cfg.bsdf_interaction_mode != GVPM_BSDF_ALL && comp > 0 && !(comp & ctx.cfg.bsdf_interaction_mode));
