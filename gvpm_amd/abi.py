@@ -119,6 +119,11 @@ assert CAMERA_RAY_DTYPE.itemsize == 64
 VPM_SAMPLE_DTYPE = np.dtype([("set", np.uint32), ("rand", np.float32), ("pdf_sel", np.float32),
                              ("reserved", np.uint32)])
 assert VPM_SAMPLE_DTYPE.itemsize == 16
+# gvpm_vpm_run, 16 bytes: samples first .. first + count - 1 share `set` and `pdf_sel` (run-packed G-VPM samples)
+VPM_RUN_DTYPE = np.dtype([("set", np.uint32), ("pdf_sel", np.float32), ("first", np.uint32), ("count", np.uint32)])
+assert VPM_RUN_DTYPE.itemsize == 16
+# the zero vector in the octahedral code of parent_n_oct / gvpm_pack_normals_oct (a medium end vertex's normal)
+GVPM_OCT_ZERO = 0x80008000
 
 
 # packed upload records (include/gvpm_hip.h, "packed uploads")

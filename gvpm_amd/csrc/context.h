@@ -359,7 +359,14 @@ struct gvpm_context {
     // (builds; the G-Planes gather itself): the next copy into the slot waits for both
     hipEvent_t consumed = nullptr, consumedB = nullptr;
     bool read = false;      // a gather has launched kernels that read it since its last copy
+    // the per-beam side arrays of a beam / plane upload (gvpm_upload_beams / _planes and their prefetch / linked twins): they
+    // live and die with the slot's beam records, ordered by the same events
+    int side = 0;             // SIDE_NONE / SIDE_BEAMS (endN) / SIDE_PLANES (w1, len1)
+    DevBuf<float> endN, w1, len1;
+    DevBuf<uint32_t> endNOct; // end normals as octahedral codes (gvpm_upload_beams_linked), decoded into endN beside `packed`
+    bool octNormals = false;
   };
+  enum : int { SIDE_NONE = 0, SIDE_BEAMS = 1, SIDE_PLANES = 2 };
   struct RaySlot {
     DevBuf<gvpm_camera_ray> rays;
     DevBuf<uint32_t> packed;  // a packed upload lands here and is decoded into rays by the consuming gather
@@ -371,14 +378,26 @@ struct gvpm_context {
     hipEvent_t copied = nullptr, freed = nullptr;
     bool read = false;      // a gather has launched kernels that read it since its last copy
   };
+  // G-VPM's camera samples: a ring of their own (they are uploaded by their own call, not with the rays)
+  struct SampleSlot {
+    DevBuf<gvpm_vpm_sample> smp;
+    DevBuf<uint32_t> packed;  // a run-packed upload: nruns runs of 4 words, then one rand per sample; expanded into smp
+    uint32_t n = 0, nruns = 0;
+    bool needUnpack = false;
+    hipEvent_t unpacked = nullptr;
+    hipEvent_t copied = nullptr, freed = nullptr;
+    bool read = false;
+  };
   template <typename Slot> struct StagingRing {
     Slot slot[3];
     int cur = 0, pending = -1;  // pending: prefetched, current after the next gather
     bool wait = false;          // the next gather's streams must wait for the current slot's copy
     bool ownedCur = false;      // the current input lives in slot[cur] (not in borrowed device memory)
+    bool fresh = false;         // the gather being queued is the first to read slot[cur] (stagingHead .. stagingTail)
   };
   StagingRing<PhotonSlot> ph;
   StagingRing<RaySlot> ray;
+  StagingRing<SampleSlot> smp;
   hipStream_t copyStream = nullptr;
   // manifold shifts through the host (gvpm_enable_host_shifts): the requests of the last G-BRE gather
   uint64_t reqCap = 0;
@@ -426,6 +445,12 @@ struct gvpm_context {
   const gvpm_camera_ray *gatheredRays = nullptr;
   uint32_t gatheredSets = 0;
   bool haveGathered = false;
+  // ... and its side arrays (gvpm_download_beam_sides: SIDE_BEAMS end normals, SIDE_PLANES w1 + len1) and G-VPM samples
+  int gatheredSide = 0;
+  const float *gatheredEndN = nullptr, *gatheredW1 = nullptr, *gatheredLen1 = nullptr;
+  const gvpm_vpm_sample *gatheredSamples = nullptr;
+  uint32_t gatheredNSamples = 0;
+  bool gatheredVpm = false;
   bool havePhotons = false, photonsDirty = false;
   bool nearOverflow = false;
   size_t nearExtWant = 0;         // entries the near-occluder extension lists asked for so far
@@ -468,7 +493,6 @@ struct gvpm_context {
   bool haveBeams = false, beamsDirty = false;
 
   // G-Beams: raw upload shares rawF/rawU/rawDev with the photons; end normals + sub-beam build
-  DevBuf<float> endNOwned;
   const float *endNDev = nullptr;
   bool haveBeamsMap = false;
   DevBuf<uint32_t> subCounts, subOffsets, beamCtl;
@@ -478,7 +502,6 @@ struct gvpm_context {
   float subLen = 0.f, maxSubLen = 0.f;
 
   // G-Planes: second edge of every plane + the 48-byte test records
-  DevBuf<float> w1Owned, len1Owned;
   const float *w1Dev = nullptr, *len1Dev = nullptr;
   DevBuf<float4> planeTest;
   DevBuf<uint32_t> subFlags;      // G-Beams: filter bits per sorted sub-beam
@@ -489,7 +512,6 @@ struct gvpm_context {
   bool havePlanes = false;
 
   // G-VPM: camera samples + per-pixel SPPM state
-  DevBuf<gvpm_vpm_sample> samplesOwned;
   const gvpm_vpm_sample *samplesDev = nullptr;
   uint32_t nsamples = 0;
   bool haveSamples = false;
@@ -578,6 +600,9 @@ void launch_unpack_linked(const uint32_t *blob, uint32_t n, const gvpm_material 
                           unsigned long long *bad, hipStream_t s);
 void launch_unpack_compact_rays(const gvpm_sensor &sensor, const uint32_t *compact, uint32_t ncompact, gvpm_camera_ray *dst,
                                 hipStream_t s);
+void launch_unpack_normals_oct(const uint32_t *codes, uint32_t n, float *dst, hipStream_t s);
+// packed: nruns gvpm_vpm_run, then n rands (checked on the host: vpmRunsOk)
+void launch_expand_vpm_runs(const uint32_t *packed, uint32_t nruns, uint32_t n, gvpm_vpm_sample *dst, hipStream_t s);
 }  // namespace gvpm
 
 // shared between the files above

@@ -1,5 +1,5 @@
-// The device decoders of the packed inputs: packed / linked photon records and packed / compact camera-beam sets into what the
-// SoA uploads put in the staging slots.  pack_codec.h defines the bytes, for these kernels and for the host unpackers
+// The device decoders of the packed inputs: packed / linked photon records, packed / compact camera-beam sets, octahedral end
+// normals and run-packed G-VPM samples into what the SoA uploads put in the staging slots.  pack_codec.h defines the bytes, for these kernels and for the host unpackers
 // (pack_host.hip) from one text; the consuming gather launches them at the head of its build chain (uploads.hip, stagingHead).
 #include "context.h"
 #include "pack_codec.h"
@@ -87,9 +87,36 @@ __global__ __launch_bounds__(256) void link_linked_kernel(const unsigned char *_
   linkChain(dst, i, i >= 2u && linkedKind(kinds, i - 1u) == GVPM_LINKED_CHAIN);
 }
 
+// ---- side inputs: end normals as octahedral codes, G-VPM samples as runs (pack_codec.h) ----
+__global__ __launch_bounds__(256) void unpack_normals_oct_kernel(const uint32_t *__restrict__ codes, uint32_t n, float *__restrict__ dst) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float v[3];
+  octDecode(codes[i], v);
+  dst[3 * (size_t)i] = v[0];
+  dst[3 * (size_t)i + 1] = v[1];
+  dst[3 * (size_t)i + 2] = v[2];
+}
+// one sample a lane, whatever the runs' lengths: each finds its run by bisection over the runs' first samples (the host has
+// checked that they ascend from 0 and end at n: vpmRunsOk), so a run of 1, of 64 or of 10 000 samples is the same code
+__global__ __launch_bounds__(256) void expand_vpm_runs_kernel(const gvpm_vpm_run *__restrict__ runs, uint32_t nruns,
+                                                              const float *__restrict__ rands, uint32_t n,
+                                                              gvpm_vpm_sample *__restrict__ dst) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = expandVpmSample(runs, nruns, rands, i);
+}
+
 }  // namespace
 
 namespace gvpm {
+void launch_unpack_normals_oct(const uint32_t *codes, uint32_t n, float *dst, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(unpack_normals_oct_kernel, dim3((n + 255) / 256), dim3(256), 0, s, codes, n, dst);
+}
+void launch_expand_vpm_runs(const uint32_t *packed, uint32_t nruns, uint32_t n, gvpm_vpm_sample *dst, hipStream_t s) {
+  if (n && nruns)
+    hipLaunchKernelGGL(expand_vpm_runs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, reinterpret_cast<const gvpm_vpm_run *>(packed),
+                       nruns, reinterpret_cast<const float *>(packed + (size_t)nruns * 4), n, dst);
+}
 void launch_unpack_linked(const uint32_t *blob, uint32_t n, const gvpm_material *table, uint32_t table_n, const gvpm_photon_soa &dst,
                           unsigned long long *bad, hipStream_t s) {
   if (!n) return;

@@ -338,6 +338,17 @@ static int gatherEntry(gvpm_context *h, int it, uint64_t nb_paths, bool primal) 
   h->gatheredRays = h->raysDev;
   h->gatheredSets = h->nsets;
   h->haveGathered = true;
+  {
+    const int t = h->cfg.vol_technique;
+    h->gatheredSide = t == GVPM_VOL_PLANE0D ? gvpm_context::SIDE_PLANES
+                      : (t == GVPM_BEAM_BEAM_1D || t == GVPM_BEAM_BEAM_3D_OPTIMIZED) ? gvpm_context::SIDE_BEAMS : gvpm_context::SIDE_NONE;
+    h->gatheredEndN = h->endNDev;
+    h->gatheredW1 = h->w1Dev;
+    h->gatheredLen1 = h->len1Dev;
+    h->gatheredVpm = t == GVPM_DISTANCE;
+    h->gatheredSamples = h->samplesDev;
+    h->gatheredNSamples = h->gatheredVpm ? h->nsamples : 0u;
+  }
   int rc;
   switch (h->cfg.vol_technique) {
     case GVPM_VOL_BRE2D:

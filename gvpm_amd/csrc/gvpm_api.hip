@@ -79,7 +79,8 @@ int gvpm_create(const gvpm_params *params, int device, gvpm_context **out) {
   }
   for (int k = 0; k < 3; ++k)
     for (hipEvent_t *e : {&h->ph.slot[k].copied, &h->ph.slot[k].unpacked, &h->ph.slot[k].consumed, &h->ph.slot[k].consumedB,
-                          &h->ray.slot[k].copied, &h->ray.slot[k].unpacked, &h->ray.slot[k].freed})
+                          &h->ray.slot[k].copied, &h->ray.slot[k].unpacked, &h->ray.slot[k].freed,
+                          &h->smp.slot[k].copied, &h->smp.slot[k].unpacked, &h->smp.slot[k].freed})
       if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) {
         gvpm_destroy(h);
         return GVPM_ERR_HIP;
@@ -222,6 +223,7 @@ int gvpm_destroy(gvpm_context *h) {
   for (auto &ps : h->ph.slot) {
     ps.raw.release();
     ps.packed.release();
+    ps.endN.release(); ps.w1.release(); ps.len1.release(); ps.endNOct.release();
     if (ps.unpacked) (void)hipEventDestroy(ps.unpacked);
     if (ps.copied) (void)hipEventDestroy(ps.copied);
     if (ps.consumed) (void)hipEventDestroy(ps.consumed);
@@ -235,15 +237,22 @@ int gvpm_destroy(gvpm_context *h) {
     if (rs.copied) (void)hipEventDestroy(rs.copied);
     if (rs.freed) (void)hipEventDestroy(rs.freed);
   }
+  for (auto &ss : h->smp.slot) {
+    ss.smp.release();
+    ss.packed.release();
+    if (ss.unpacked) (void)hipEventDestroy(ss.unpacked);
+    if (ss.copied) (void)hipEventDestroy(ss.copied);
+    if (ss.freed) (void)hipEventDestroy(ss.freed);
+  }
   if (h->copyStream) (void)hipStreamDestroy(h->copyStream);
   h->materials.release();
   h->reqHost.release(); h->reqCtx.release(); h->reqCount.release(); h->reqResults.release();
-  h->endNOwned.release(); h->subCounts.release(); h->subOffsets.release();
+  h->subCounts.release(); h->subOffsets.release();
   h->beamCtl.release(); h->beamAux.release(); h->beamClear.release();
   h->nearGridStart.release(); h->nearGridTris.release(); h->nearGridCount.release();
-  h->w1Owned.release(); h->len1Owned.release(); h->planeTest.release(); h->beamPairs.release(); h->subFlags.release(); h->shiftExtent.release();
+  h->planeTest.release(); h->beamPairs.release(); h->subFlags.release(); h->shiftExtent.release();
   h->blockKeyA.release(); h->blockKeyB.release(); h->blockValA.release(); h->blockValB.release();
-  h->samplesOwned.release(); h->scaleVol.release(); h->nVol.release(); h->mvol.release(); h->maxScaleBits.release();
+  h->scaleVol.release(); h->nVol.release(); h->mvol.release(); h->maxScaleBits.release();
   poisson_graph_release(h->poissonGraph);
   h->accumTmp.release();
   h->chainCtl.release();

@@ -146,6 +146,34 @@ GVPM_HD void linkChain(const gvpm_photon_soa &d, uint64_t i, bool prevChain) {
   deriveWi(d.pos + 3 * i, ppos, wi);
 }
 
+// ---- run-packed G-VPM samples (include/gvpm_hip.h) ----
+// a run list as the header states it: contiguous from sample 0, no empty run, counts summing to n
+inline bool vpmRunsOk(const gvpm_vpm_run *runs, uint64_t n_runs, uint64_t n) {
+  if (n_runs && !runs) return false;
+  uint64_t next = 0;
+  for (uint64_t r = 0; r < n_runs; ++r) {
+    if (runs[r].count == 0u || runs[r].first != next) return false;
+    next += runs[r].count;
+    if (next > 0xFFFFFFFFull) return false;
+  }
+  return next == n;
+}
+// sample i of n_runs >= 1 checked runs: the last run that starts at or before it
+GVPM_HD gvpm_vpm_sample expandVpmSample(const gvpm_vpm_run *runs, uint32_t n_runs, const float *rands, uint32_t i) {
+  uint32_t lo = 0u, hi = n_runs;  // runs[lo].first <= i < runs[hi].first (hi == n_runs: the end)
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if (runs[mid].first <= i) lo = mid;
+    else hi = mid;
+  }
+  gvpm_vpm_sample s;
+  s.set = runs[lo].set;
+  s.rand = rands[i];
+  s.pdf_sel = runs[lo].pdf_sel;
+  s.reserved = 0u;
+  return s;
+}
+
 // ray k (0: base, 1..4: shifted) of a packed beam set -> a full camera ray
 GVPM_HD gvpm_camera_ray unpackRay(const gvpm_beam_set_packed &s, int k) {
   if (k == 0) return s.base;

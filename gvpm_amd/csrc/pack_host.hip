@@ -1,5 +1,5 @@
 // The host codecs of the packed inputs (C ABI, include/gvpm_hip.h): gvpm_pack_* / gvpm_unpack_* for packed and linked photon
-// records and packed / compact camera-beam sets.  Host only: no handle, no device.  pack_codec.h defines the decode, shared
+// records, packed / compact camera-beam sets, octahedral end normals and run-packed G-VPM samples.  Host only: no handle, no device.  pack_codec.h defines the decode, shared
 // with the device decoders (decode_device.hip).
 #include <algorithm>
 #include <vector>
@@ -23,6 +23,45 @@ uint32_t octEncode(const float v[3]) {
   }
   const long ix = std::lrint(px * 32767.0), iy = std::lrint(py * 32767.0);
   return ((uint32_t)(int16_t)ix & 0xFFFFu) | ((uint32_t)(int16_t)iy << 16);
+}
+
+// ... the NEAREST code: of the four lattice points around the vector's image, the one whose decode makes the smallest angle
+// with it.  Rounding each coordinate (octEncode) is off by up to 6.4e-5 rad in general position -- the third coordinate of the
+// decode moves with both -- the nearest code by 4.3e-5.  Same code, same decode; the photon records keep octEncode, whose
+// bytes existing blobs and results depend on.
+uint32_t octEncodeNearest(const float v[3]) {
+  const double x = v[0], y = v[1], z = v[2];
+  const double l1 = std::fabs(x) + std::fabs(y) + std::fabs(z), l2 = std::sqrt(x * x + y * y + z * z);
+  if (!(l1 > 0.0) || !std::isfinite(l1)) return GVPM_OCT_ZERO;
+  double px = x / l1, py = y / l1;
+  if (z < 0.0) {
+    const double fx = (1.0 - std::fabs(py)) * (px >= 0.0 ? 1.0 : -1.0), fy = (1.0 - std::fabs(px)) * (py >= 0.0 ? 1.0 : -1.0);
+    px = fx;
+    py = fy;
+  }
+  const double bx = std::floor(px * 32767.0), by = std::floor(py * 32767.0);
+  double bestErr = 1e300;
+  long bestX = 0, bestY = 0;
+  for (int k = 0; k < 4; ++k) {
+    const long ix = std::min(32767L, std::max(-32767L, (long)bx + (k & 1))), iy = std::min(32767L, std::max(-32767L, (long)by + (k >> 1)));
+    // octDecode's arithmetic, kept in fp64
+    double dx = (double)ix / 32767.0, dy = (double)iy / 32767.0;
+    const double dz = 1.0 - std::fabs(dx) - std::fabs(dy);
+    if (dz < 0.0) {
+      const double fx = (1.0 - std::fabs(dy)) * (dx >= 0.0 ? 1.0 : -1.0), fy = (1.0 - std::fabs(dx)) * (dy >= 0.0 ? 1.0 : -1.0);
+      dx = fx;
+      dy = fy;
+    }
+    const double len = std::sqrt(dx * dx + dy * dy + dz * dz);
+    const double ex = dx / len - x / l2, ey = dy / len - y / l2, ez = dz / len - z / l2;
+    const double err = ex * ex + ey * ey + ez * ez;
+    if (err < bestErr) {
+      bestErr = err;
+      bestX = ix;
+      bestY = iy;
+    }
+  }
+  return ((uint32_t)(int16_t)bestX & 0xFFFFu) | ((uint32_t)(int16_t)bestY << 16);
 }
 
 // the index of photon i's parent material in `table`, appended if it is new; false: the table is full
@@ -327,6 +366,46 @@ int gvpm_unpack_camera_beams(const gvpm_beam_set_packed *src, uint64_t n_sets, g
   if (n_sets && (!src || !dst)) return GVPM_ERR_INVALID_ARG;
   for (uint64_t i = 0; i < n_sets; ++i)
     for (int k = 0; k < 5; ++k) dst[5 * i + k] = unpackRay(src[i], k);
+  return GVPM_OK;
+}
+
+// ---- the side inputs of the beam / plane / G-VPM techniques (include/gvpm_hip.h) ----
+int gvpm_pack_normals_oct(const float *normals, uint64_t n, uint32_t *codes) {
+  if (n && (!normals || !codes)) return GVPM_ERR_INVALID_ARG;
+  for (uint64_t i = 0; i < n; ++i) codes[i] = octEncodeNearest(normals + 3 * i);
+  return GVPM_OK;
+}
+
+int gvpm_unpack_normals_oct(const uint32_t *codes, uint64_t n, float *normals) {
+  if (n && (!codes || !normals)) return GVPM_ERR_INVALID_ARG;
+  for (uint64_t i = 0; i < n; ++i) octDecode(codes[i], normals + 3 * i);
+  return GVPM_OK;
+}
+
+int gvpm_pack_vpm_samples(const gvpm_vpm_sample *samples, uint64_t n, gvpm_vpm_run *runs, uint64_t runs_cap, uint64_t *n_runs,
+                          float *rands) {
+  if (!n_runs || n > 0x7FFFFFF0ull || (n && (!samples || !runs || !rands))) return GVPM_ERR_INVALID_ARG;
+  uint64_t nr = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const gvpm_vpm_sample &s = samples[i];
+    if (s.reserved != 0u) return GVPM_ERR_INVALID_ARG;
+    // (bit-equal: -0 and 0, or two NaNs, are not one run -- the decode must give back the bytes)
+    const bool same = nr > 0 && runs[nr - 1].set == s.set && memcmp(&runs[nr - 1].pdf_sel, &s.pdf_sel, 4) == 0;
+    if (same) {
+      runs[nr - 1].count++;
+    } else {
+      if (nr >= runs_cap) return GVPM_ERR_INVALID_ARG;
+      runs[nr++] = gvpm_vpm_run{s.set, s.pdf_sel, (uint32_t)i, 1u};
+    }
+    rands[i] = s.rand;
+  }
+  *n_runs = nr;
+  return GVPM_OK;
+}
+
+int gvpm_unpack_vpm_samples(const gvpm_vpm_run *runs, uint64_t n_runs, const float *rands, uint64_t n, gvpm_vpm_sample *dst) {
+  if (n > 0x7FFFFFF0ull || (n && (!rands || !dst)) || !vpmRunsOk(runs, n_runs, n)) return GVPM_ERR_INVALID_ARG;
+  for (uint64_t i = 0; i < n; ++i) dst[i] = expandVpmSample(runs, (uint32_t)n_runs, rands, (uint32_t)i);
   return GVPM_OK;
 }
 

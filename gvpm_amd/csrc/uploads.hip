@@ -7,8 +7,10 @@
 
 using PhotonSlot = gvpm_context::PhotonSlot;
 using RaySlot = gvpm_context::RaySlot;
+using SampleSlot = gvpm_context::SampleSlot;
 using PhotonRing = gvpm_context::StagingRing<PhotonSlot>;
 using RayRing = gvpm_context::StagingRing<RaySlot>;
+using SampleRing = gvpm_context::StagingRing<SampleSlot>;
 
 static bool isPinnedHost(const void *ptr) {
   hipPointerAttribute_t attr;
@@ -32,12 +34,34 @@ static int waitForReaders(gvpm_context *h, RaySlot &rs) {
   HIP_TRY(h, hipStreamWaitEvent(h->copyStream, rs.freed, 0));
   return GVPM_OK;
 }
+static int waitForReaders(gvpm_context *h, SampleSlot &ss) {
+  // G-VPM's kernels read the samples (the redo on its side stream is joined back before the gather's tail)
+  HIP_TRY(h, hipStreamWaitEvent(h->copyStream, ss.freed, 0));
+  return GVPM_OK;
+}
 static void makeCurrent(gvpm_context *h, PhotonRing &r, int slot) {
   r.cur = slot;
   r.wait = r.ownedCur = true;
-  h->rawDev = r.slot[slot].dev;
+  const PhotonSlot &ps = r.slot[slot];
+  h->rawDev = ps.dev;
   h->nph = (uint32_t)h->rawDev.n;
   h->havePhotons = h->photonsDirty = true;
+  // the side arrays the slot carries (a plain photon upload carries none: the techniques that need them keep what they had)
+  if (ps.side == gvpm_context::SIDE_BEAMS) {
+    h->endNDev = ps.endN.p;
+    h->haveBeamsMap = true;
+  } else if (ps.side == gvpm_context::SIDE_PLANES) {
+    h->w1Dev = ps.w1.p;
+    h->len1Dev = ps.len1.p;
+    h->havePlanes = true;
+  }
+}
+static void makeCurrent(gvpm_context *h, SampleRing &r, int slot) {
+  r.cur = slot;
+  r.wait = r.ownedCur = true;
+  h->samplesDev = r.slot[slot].smp.p;
+  h->nsamples = r.slot[slot].n;
+  h->haveSamples = true;
 }
 static void makeCurrent(gvpm_context *h, RayRing &r, int slot) {
   r.cur = slot;
@@ -65,6 +89,7 @@ static int acquireSlot(gvpm_context *h, gvpm_context::StagingRing<Slot> &r, bool
 }
 static const char *const PHOTONS_PENDING = "a prefetched photon set is already pending";
 static const char *const BEAMS_PENDING = "a prefetched camera-beam list is already pending";
+static const char *const SAMPLES_PENDING = "a prefetched set of vpm samples is already pending";
 
 // Before a slot's buffers are regrown: regrowing frees the old ones, which a build or a decode on either compute stream, or
 // a copy, may still be using.  All three streams whatever the format: DevBuf::ensure's hipFree is a device-wide sync as it is,
@@ -82,8 +107,8 @@ static int finishSlot(gvpm_context *h, gvpm_context::StagingRing<Slot> &r, Slot 
   HIP_TRY(h, hipEventRecord(s->copied, h->copyStream));
   // pageable memory: the caller may reuse its buffers when this returns (one pageable array makes the runtime stage that copy
   // itself; the header's contract: the library copies during the call).  Pinned memory (gvpm_host_alloc*): the copy is left
-  // in flight; the buffer must stay untouched until the gather that consumes it has returned (G-BRE) or the handle was
-  // synchronised
+  // in flight; the buffer must stay untouched until the gather that consumes it has returned (copyDoneAtTail) or the handle
+  // was synchronised
   if (!pinned) HIP_TRY(h, hipStreamSynchronize(h->copyStream));
   const int slot = (int)(s - r.slot);
   if (prefetch) r.pending = slot;
@@ -107,6 +132,16 @@ static int awaitCurrent(gvpm_context *h, gvpm_context::StagingRing<Slot> &r, hip
     s.needUnpack = false;
   }
   r.wait = false;
+  r.fresh = true;
+  return GVPM_OK;
+}
+// The header's lifetime rule for pinned buffers -- untouched until the gather that consumes them has returned -- holds by
+// itself where the gather waits on the host for a kernel behind the copy (G-BRE's build, G-Beams' bounds).  G-Planes and
+// G-VPM's samples have no such wait: the gather's tail waits for the copy it has just consumed (long complete: its kernels
+// are queued behind it).  G-BRE's tail does not pay for the call.
+template <typename Ring> static int copyDoneAtTail(gvpm_context *h, Ring &r, bool wait) {
+  if (r.fresh && wait && r.ownedCur) HIP_TRY(h, hipEventSynchronize(r.slot[r.cur].copied));
+  r.fresh = false;
   return GVPM_OK;
 }
 // prefetched inputs (gvpm_prefetch_*) become the current ones: what an upload at this point would have done
@@ -124,6 +159,12 @@ int stagingHead(gvpm_context *h, hipStream_t us, hipStream_t other) {
       return fail(h, GVPM_ERR_STATE, "packed photons were uploaded but no material table (gvpm_upload_materials)");
     if (ps.linked) launch_unpack_linked(ps.packed.p, (uint32_t)ps.dev.n, h->materials.p, h->nmaterials, ps.dev, h->stats.p + 6, us);
     else launch_unpack_photons(ps.packed.p, (uint32_t)ps.dev.n, h->materials.p, h->nmaterials, ps.dev, h->stats.p + 6, us);
+    if (ps.octNormals) launch_unpack_normals_oct(ps.endNOct.p, (uint32_t)ps.dev.n, ps.endN.p, us);
+    return (int)GVPM_OK;
+  });
+  if (rc != GVPM_OK) return rc;
+  rc = awaitCurrent(h, h->smp, us, other, [&](SampleSlot &ss) {
+    launch_expand_vpm_runs(ss.packed.p, ss.nruns, ss.n, ss.smp.p, us);
     return (int)GVPM_OK;
   });
   if (rc != GVPM_OK) return rc;
@@ -144,7 +185,17 @@ int stagingTail(gvpm_context *h) {
     HIP_TRY(h, hipEventRecord(rs.freed, h->stream));
     rs.read = true;
   }
+  // ... of G-VPM's samples
+  if (h->smp.ownedCur) {
+    SampleSlot &ss = h->smp.slot[h->smp.cur];
+    HIP_TRY(h, hipEventRecord(ss.freed, h->stream));
+    ss.read = true;
+  }
   // ... and of the staged photon arrays (the build on either stream; G-Planes reads them in the gather itself)
+  const bool breTech = h->cfg.vol_technique == GVPM_VOL_BRE2D || h->cfg.vol_technique == GVPM_VOL_BRE3D;
+  if (int rc = copyDoneAtTail(h, h->ph, !breTech)) return rc;
+  if (int rc = copyDoneAtTail(h, h->ray, !breTech)) return rc;
+  if (int rc = copyDoneAtTail(h, h->smp, !breTech)) return rc;
   if (h->ph.ownedCur) {
     // G-BRE reads them in its build only (reorder_kernel), and gatherBRE has waited for that build on the host (the
     // planner's counters): nothing of it is in flight here.  An event behind the whole gather made the prefetched copy
@@ -160,11 +211,55 @@ int stagingTail(gvpm_context *h) {
   }
   promotePending(h, h->ph);
   promotePending(h, h->ray);
+  promotePending(h, h->smp);
   return GVPM_OK;
 }
 
 // ---- the uploads into the ring: each its argument checks, its capacity needs and its copies --------------------------------
-static int uploadPhotonsCommon(gvpm_context *h, const gvpm_photon_soa *p, bool fromDevice, bool prefetch = false) {
+// The per-beam side arrays that ride in a photon slot beside its beam records: end normals (fp32, or one octahedral code a
+// beam) for G-Beams, the second plane edges for G-Planes.  Host pointers.
+struct SideArrays {
+  int kind = gvpm_context::SIDE_NONE;
+  const float *endN = nullptr;
+  const uint32_t *endNOct = nullptr;
+  const float *w1 = nullptr, *len1 = nullptr;
+  const char *needsPinned = nullptr;  // the refusal of a prefetch from pageable memory, in the entry point's name
+};
+static bool sidePinned(const SideArrays &sd) {
+  for (const void *q : {(const void *)sd.endN, (const void *)sd.endNOct, (const void *)sd.w1, (const void *)sd.len1})
+    if (q && !isPinnedHost(q)) return false;
+  return true;
+}
+static bool sideFits(const PhotonSlot &ps, const SideArrays &sd, size_t n) {
+  if (sd.kind == gvpm_context::SIDE_BEAMS) return ps.endN.cap >= n * 3 + 4 && (!sd.endNOct || ps.endNOct.cap >= n + 4);
+  if (sd.kind == gvpm_context::SIDE_PLANES) return ps.w1.cap >= n * 3 + 4 && ps.len1.cap >= n + 4;
+  return true;
+}
+// (after syncBeforeRegrow)
+static int growSide(gvpm_context *h, PhotonSlot &ps, const SideArrays &sd, size_t n) {
+  if (sd.kind == gvpm_context::SIDE_BEAMS) {
+    HIP_TRY(h, ps.endN.ensure(n * 3 + 4));
+    if (sd.endNOct) HIP_TRY(h, ps.endNOct.ensure(n + 4));
+  } else if (sd.kind == gvpm_context::SIDE_PLANES) {
+    HIP_TRY(h, ps.w1.ensure(n * 3 + 4));
+    HIP_TRY(h, ps.len1.ensure(n + 4));
+  }
+  return GVPM_OK;
+}
+// on the copy stream, behind the slot's beam records and in front of its `copied`
+static int copySide(gvpm_context *h, PhotonSlot &ps, const SideArrays &sd, size_t n) {
+  ps.side = sd.kind;
+  ps.octNormals = n > 0 && sd.endNOct != nullptr;
+  if (!n) return GVPM_OK;
+  if (sd.endNOct) HIP_TRY(h, hipMemcpyAsync(ps.endNOct.p, sd.endNOct, n * 4, hipMemcpyHostToDevice, h->copyStream));
+  else if (sd.endN) HIP_TRY(h, hipMemcpyAsync(ps.endN.p, sd.endN, n * 12, hipMemcpyHostToDevice, h->copyStream));
+  if (sd.w1) HIP_TRY(h, hipMemcpyAsync(ps.w1.p, sd.w1, n * 12, hipMemcpyHostToDevice, h->copyStream));
+  if (sd.len1) HIP_TRY(h, hipMemcpyAsync(ps.len1.p, sd.len1, n * 4, hipMemcpyHostToDevice, h->copyStream));
+  return GVPM_OK;
+}
+
+static int uploadPhotonsCommon(gvpm_context *h, const gvpm_photon_soa *p, bool fromDevice, bool prefetch = false,
+                               const SideArrays &sd = SideArrays()) {
   if (!p) return fail(h, GVPM_ERR_INVALID_ARG, "null photon soa");
   if (p->n > 0x7FFFFFF0ull) return fail(h, GVPM_ERR_INVALID_ARG, "too many photons");
   const uint32_t n = (uint32_t)p->n;
@@ -189,12 +284,18 @@ static int uploadPhotonsCommon(gvpm_context *h, const gvpm_photon_soa *p, bool f
   // pinned only if EVERY array is
   bool pinned = n > 0;
   for (int k = 0; k < (oneBlock ? 1 : PHOTON_ARRAYS) && pinned; ++k) pinned = isPinnedHost(src.p[k]);
+  // (an EMPTY beam / plane set may be prefetched like any other: its pointers, where given, say where it comes from)
+  if (n == 0 && sd.kind != gvpm_context::SIDE_NONE) pinned = src.p[0] && isPinnedHost(src.p[0]);
+  pinned = pinned && sidePinned(sd);
   PhotonSlot *ps;
-  if (int rc = acquireSlot(h, h->ph, prefetch, pinned, "gvpm_prefetch_photons needs pinned host memory (gvpm_host_alloc*)", PHOTONS_PENDING, &ps))
+  if (int rc = acquireSlot(h, h->ph, prefetch, pinned,
+                           sd.needsPinned ? sd.needsPinned : "gvpm_prefetch_photons needs pinned host memory (gvpm_host_alloc*)",
+                           PHOTONS_PENDING, &ps))
     return rc;
-  if (ps->raw.cap < (size_t)n * PHOTON_WORDS + 8) {
+  if (ps->raw.cap < (size_t)n * PHOTON_WORDS + 8 || !sideFits(*ps, sd, n)) {
     if (int rc = syncBeforeRegrow(h)) return rc;
     HIP_TRY(h, ps->raw.ensure((size_t)n * PHOTON_WORDS + 8));
+    if (int rc = growSide(h, *ps, sd, n)) return rc;
   }
   photonArraysInBlock(ps->dev, ps->raw.p, n);
   ps->needUnpack = ps->linked = false;
@@ -204,6 +305,7 @@ static int uploadPhotonsCommon(gvpm_context *h, const gvpm_photon_soa *p, bool f
     HIP_TRY(h, hipMemcpyAsync(to, src.p[k], (size_t)n * photonArrayWords(k) * 4, hipMemcpyHostToDevice, h->copyStream));
     to += (size_t)n * photonArrayWords(k);
   }
+  if (int rc = copySide(h, *ps, sd, n)) return rc;
   return finishSlot(h, h->ph, ps, pinned, prefetch);
 }
 
@@ -212,19 +314,25 @@ static int uploadPhotonsCommon(gvpm_context *h, const gvpm_photon_soa *p, bool f
 // sit between two copies and wait for compute units behind the gather kernels of the step in flight -- measured at C2,
 // 4.7 ms a step that way against 3.6 for the SoA upload it was to beat
 // (linkedBytes != 0: `src` is a blob of linked records of that size, n64 its photon count)
-static int uploadPhotonsPacked(gvpm_context *h, const gvpm_photon_packed *src, uint64_t n64, bool prefetch, size_t linkedBytes = 0) {
+static int uploadPhotonsPacked(gvpm_context *h, const gvpm_photon_packed *src, uint64_t n64, bool prefetch, size_t linkedBytes = 0,
+                               const SideArrays &sd = SideArrays()) {
   if (n64 && !src) return fail(h, GVPM_ERR_INVALID_ARG, "null packed photons");
   if (n64 > 0x7FFFFFF0ull) return fail(h, GVPM_ERR_INVALID_ARG, "too many photons");
   const uint32_t n = (uint32_t)n64;
-  const bool pinned = n > 0 && isPinnedHost(src);
+  bool pinned = n > 0 && isPinnedHost(src);
+  if (n == 0 && sd.kind != gvpm_context::SIDE_NONE) pinned = src && isPinnedHost(src);  // (an empty beam / plane set: uploadPhotonsCommon)
+  pinned = pinned && sidePinned(sd);
   PhotonSlot *ps;
-  if (int rc = acquireSlot(h, h->ph, prefetch, pinned, "gvpm_prefetch_photons_packed needs pinned host memory (gvpm_host_alloc)", PHOTONS_PENDING, &ps))
+  if (int rc = acquireSlot(h, h->ph, prefetch, pinned,
+                           sd.needsPinned ? sd.needsPinned : "gvpm_prefetch_photons_packed needs pinned host memory (gvpm_host_alloc)",
+                           PHOTONS_PENDING, &ps))
     return rc;
   constexpr size_t RW = sizeof(gvpm_photon_packed) / 4;
   const size_t packedWords = linkedBytes ? (linkedBytes + 3u) / 4u + 8u : (size_t)n * RW + 8;
-  if (ps->raw.cap < (size_t)n * PHOTON_WORDS + 8 || ps->packed.cap < packedWords) {
+  if (ps->raw.cap < (size_t)n * PHOTON_WORDS + 8 || ps->packed.cap < packedWords || !sideFits(*ps, sd, n)) {
     if (int rc = syncBeforeRegrow(h)) return rc;
     HIP_TRY(h, ps->raw.ensure((size_t)n * PHOTON_WORDS + 8));
+    if (int rc = growSide(h, *ps, sd, n)) return rc;
     // (a blob of linked records is never larger than the packed records of its photons + its tables: sized for those, so that
     // blobs of varying size do not regrow the slot)
     HIP_TRY(h, ps->packed.ensure(std::max(packedWords, (size_t)n * RW + 8 + 16384u)));
@@ -233,52 +341,82 @@ static int uploadPhotonsPacked(gvpm_context *h, const gvpm_photon_packed *src, u
   ps->needUnpack = n > 0;
   ps->linked = linkedBytes != 0;
   if (n) HIP_TRY(h, hipMemcpyAsync(ps->packed.p, src, linkedBytes ? linkedBytes : (size_t)n * sizeof(gvpm_photon_packed), hipMemcpyHostToDevice, h->copyStream));
+  if (int rc = copySide(h, *ps, sd, n)) return rc;
   return finishSlot(h, h->ph, ps, pinned, prefetch);
 }
 
-static int uploadLinked(gvpm_context *h, const void *blob, size_t bytes, bool prefetch) {
+static int uploadLinked(gvpm_context *h, const void *blob, size_t bytes, bool prefetch, const SideArrays &sd = SideArrays()) {
   if (!blob || bytes < sizeof(gvpm_linked_header)) return fail(h, GVPM_ERR_INVALID_ARG, "null or short blob of linked photon records");
   gvpm_linked_header hd;
   memcpy(&hd, blob, sizeof(hd));
+  if (sd.kind != gvpm_context::SIDE_NONE && hd.n > 0xFFFFFFu) return fail(h, GVPM_ERR_INVALID_ARG, "too many beams (24-bit beam index)");
   if (!linkedHeaderOk(hd, bytes)) return fail(h, GVPM_ERR_INVALID_ARG, "not a blob of gvpm_pack_photons_linked (header / sizes)");
-  if (hd.n == 0u) return uploadPhotonsPacked(h, nullptr, 0, prefetch);
-  return uploadPhotonsPacked(h, static_cast<const gvpm_photon_packed *>(blob), hd.n, prefetch, hd.bytes);
+  // (an empty blob of beams keeps its pointer: it says whether the set comes from pinned memory)
+  if (hd.n == 0u) return uploadPhotonsPacked(h, sd.kind != gvpm_context::SIDE_NONE ? static_cast<const gvpm_photon_packed *>(blob) : nullptr, 0, prefetch, 0, sd);
+  return uploadPhotonsPacked(h, static_cast<const gvpm_photon_packed *>(blob), hd.n, prefetch, hd.bytes, sd);
 }
 
-// a side array of the current input (end normals, second plane edges, G-VPM samples): borrowed device memory, or copied on
-// the gather stream during the call
-template <typename T>
-static int uploadSideArray(gvpm_context *h, DevBuf<T> &owned, const T *&dev, const T *src, size_t n, size_t pad, bool fromDevice) {
-  if (!fromDevice) {
-    HIP_TRY(h, owned.ensure(n + pad));
-    if (n) {
-      HIP_TRY(h, hipMemcpyAsync(owned.p, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-  }
-  dev = fromDevice ? src : owned.p;
-  return GVPM_OK;
-}
-
-static int uploadPhotonBeamsCommon(gvpm_context *h, const gvpm_photon_soa *b, const float *end_n, bool fromDevice) {
+// Photon beams and planes: a photon upload whose slot also carries the side arrays (host memory), or borrowed device memory
+static const char *const BEAMS_NEED_PINNED = "gvpm_prefetch_beams* needs pinned host memory (gvpm_host_alloc*), end normals included";
+static const char *const PLANES_NEED_PINNED = "gvpm_prefetch_planes* needs pinned host memory (gvpm_host_alloc*), w1 and len1 included";
+static int uploadPhotonBeamsCommon(gvpm_context *h, const gvpm_photon_soa *b, const float *end_n, bool fromDevice, bool prefetch = false) {
   if (b && b->n && !end_n) return fail(h, GVPM_ERR_INVALID_ARG, "null end_n");
   if (b && b->n > 0xFFFFFFull) return fail(h, GVPM_ERR_INVALID_ARG, "too many beams (24-bit beam index)");
-  int rc = uploadPhotonsCommon(h, b, fromDevice);
-  if (rc == GVPM_OK) rc = uploadSideArray(h, h->endNOwned, h->endNDev, end_n, (size_t)h->nph * 3, 4, fromDevice);
-  if (rc != GVPM_OK) return rc;
-  h->haveBeamsMap = true;
+  SideArrays sd;
+  sd.kind = gvpm_context::SIDE_BEAMS;
+  sd.endN = end_n;
+  sd.needsPinned = BEAMS_NEED_PINNED;
+  if (int rc = uploadPhotonsCommon(h, b, fromDevice, prefetch, sd)) return rc;
+  if (fromDevice) {
+    h->endNDev = end_n;
+    h->haveBeamsMap = true;
+  }
   return GVPM_OK;
 }
 
-static int uploadPlanesCommon(gvpm_context *h, const gvpm_photon_soa *b, const float *w1, const float *len1,
-                              bool fromDevice) {
+static int uploadPlanesCommon(gvpm_context *h, const gvpm_photon_soa *b, const float *w1, const float *len1, bool fromDevice,
+                              bool prefetch = false) {
   if (b && b->n && (!w1 || !len1)) return fail(h, GVPM_ERR_INVALID_ARG, "null w1 / len1");
-  int rc = uploadPhotonsCommon(h, b, fromDevice);
-  if (rc == GVPM_OK) rc = uploadSideArray(h, h->w1Owned, h->w1Dev, w1, (size_t)h->nph * 3, 4, fromDevice);
-  if (rc == GVPM_OK) rc = uploadSideArray(h, h->len1Owned, h->len1Dev, len1, (size_t)h->nph, 4, fromDevice);
-  if (rc != GVPM_OK) return rc;
-  h->havePlanes = true;
+  // (the synchronous entry points never had G-Beams' limit; the prefetch ones state it)
+  if (prefetch && b && b->n > 0xFFFFFFull) return fail(h, GVPM_ERR_INVALID_ARG, "too many planes (24-bit beam index)");
+  SideArrays sd;
+  sd.kind = gvpm_context::SIDE_PLANES;
+  sd.w1 = w1;
+  sd.len1 = len1;
+  sd.needsPinned = PLANES_NEED_PINNED;
+  if (int rc = uploadPhotonsCommon(h, b, fromDevice, prefetch, sd)) return rc;
+  if (fromDevice) {
+    h->w1Dev = w1;
+    h->len1Dev = len1;
+    h->havePlanes = true;
+  }
   return GVPM_OK;
+}
+
+static int uploadBeamsLinked(gvpm_context *h, const void *blob, size_t bytes, const uint32_t *end_n_oct, bool prefetch) {
+  SideArrays sd;
+  sd.kind = gvpm_context::SIDE_BEAMS;
+  sd.endNOct = end_n_oct;
+  sd.needsPinned = BEAMS_NEED_PINNED;
+  if (blob && bytes >= sizeof(gvpm_linked_header)) {
+    gvpm_linked_header hd;
+    memcpy(&hd, blob, sizeof(hd));
+    if (hd.n && hd.n <= 0xFFFFFFu && !end_n_oct) return fail(h, GVPM_ERR_INVALID_ARG, "null end_n_oct");
+  }
+  return uploadLinked(h, blob, bytes, prefetch, sd);
+}
+static int uploadPlanesLinked(gvpm_context *h, const void *blob, size_t bytes, const float *w1, const float *len1, bool prefetch) {
+  SideArrays sd;
+  sd.kind = gvpm_context::SIDE_PLANES;
+  sd.w1 = w1;
+  sd.len1 = len1;
+  sd.needsPinned = PLANES_NEED_PINNED;
+  if (blob && bytes >= sizeof(gvpm_linked_header)) {
+    gvpm_linked_header hd;
+    memcpy(&hd, blob, sizeof(hd));
+    if (hd.n && hd.n <= 0xFFFFFFu && (!w1 || !len1)) return fail(h, GVPM_ERR_INVALID_ARG, "null w1 / len1");
+  }
+  return uploadLinked(h, blob, bytes, prefetch, sd);
 }
 
 static int uploadBeamsCommon(gvpm_context *h, const gvpm_camera_ray *rays, uint64_t nsets, bool fromDevice,
@@ -357,13 +495,57 @@ static int uploadBeamsCompact(gvpm_context *h, const gvpm_beam_set_compact *comp
   return finishSlot(h, h->ray, rs, pinned, prefetch);
 }
 
-static int uploadSamplesCommon(gvpm_context *h, const gvpm_vpm_sample *smp, uint64_t n, bool fromDevice) {
+static int uploadSamplesCommon(gvpm_context *h, const gvpm_vpm_sample *smp, uint64_t n, bool fromDevice, bool prefetch = false) {
   if (n && !smp) return fail(h, GVPM_ERR_INVALID_ARG, "null vpm samples");
   if (n > 0x7FFFFFF0ull) return fail(h, GVPM_ERR_INVALID_ARG, "too many vpm samples");
-  if (int rc = uploadSideArray(h, h->samplesOwned, h->samplesDev, smp, (size_t)n, 1, fromDevice)) return rc;
-  h->nsamples = (uint32_t)n;
-  h->haveSamples = true;
-  return GVPM_OK;
+  if (fromDevice) {
+    if (prefetch) return fail(h, GVPM_ERR_INVALID_ARG, "prefetch takes host buffers");
+    h->samplesDev = smp;
+    h->smp.wait = h->smp.ownedCur = false;
+    h->nsamples = (uint32_t)n;
+    h->haveSamples = true;
+    return GVPM_OK;
+  }
+  const bool pinned = n && isPinnedHost(smp);
+  SampleSlot *ss;
+  if (int rc = acquireSlot(h, h->smp, prefetch, pinned, "gvpm_prefetch_vpm_samples needs pinned host memory (gvpm_host_alloc)", SAMPLES_PENDING, &ss))
+    return rc;
+  if (ss->smp.cap < (size_t)n + 1) {
+    if (int rc = syncBeforeRegrow(h)) return rc;
+    HIP_TRY(h, ss->smp.ensure((size_t)n + 1));
+  }
+  ss->n = (uint32_t)n;
+  ss->nruns = 0;
+  ss->needUnpack = false;
+  if (n) HIP_TRY(h, hipMemcpyAsync(ss->smp.p, smp, (size_t)n * sizeof(gvpm_vpm_sample), hipMemcpyHostToDevice, h->copyStream));
+  return finishSlot(h, h->smp, ss, pinned, prefetch);
+}
+
+// the run-packed twin: the runs and one rand a sample land in the slot's `packed`, expanded by the consuming gather
+static int uploadSamplesPacked(gvpm_context *h, const gvpm_vpm_run *runs, uint64_t nruns, const float *rands, uint64_t n, bool prefetch) {
+  if (n > 0x7FFFFFF0ull) return fail(h, GVPM_ERR_INVALID_ARG, "too many vpm samples");
+  if (n && !rands) return fail(h, GVPM_ERR_INVALID_ARG, "null rands");
+  if (!vpmRunsOk(runs, nruns, n))
+    return fail(h, GVPM_ERR_INVALID_ARG, "vpm sample runs: contiguous from sample 0, none empty, counts summing to n (gvpm_unpack_vpm_samples)");
+  const bool pinned = n && isPinnedHost(runs) && isPinnedHost(rands);
+  SampleSlot *ss;
+  if (int rc = acquireSlot(h, h->smp, prefetch, pinned, "gvpm_prefetch_vpm_samples_packed needs pinned host memory (gvpm_host_alloc)", SAMPLES_PENDING, &ss))
+    return rc;
+  const size_t words = (size_t)nruns * 4 + (size_t)n + 8;
+  if (ss->smp.cap < (size_t)n + 1 || ss->packed.cap < words) {
+    if (int rc = syncBeforeRegrow(h)) return rc;
+    HIP_TRY(h, ss->smp.ensure((size_t)n + 1));
+    // (room for a run every fourth sample: lists of varying length seldom regrow the slot)
+    HIP_TRY(h, ss->packed.ensure(std::max(words, (size_t)n * 2 + 8)));
+  }
+  ss->n = (uint32_t)n;
+  ss->nruns = (uint32_t)nruns;
+  ss->needUnpack = n > 0;
+  if (n) {
+    HIP_TRY(h, hipMemcpyAsync(ss->packed.p, runs, (size_t)nruns * sizeof(gvpm_vpm_run), hipMemcpyHostToDevice, h->copyStream));
+    HIP_TRY(h, hipMemcpyAsync(ss->packed.p + (size_t)nruns * 4, rands, (size_t)n * 4, hipMemcpyHostToDevice, h->copyStream));
+  }
+  return finishSlot(h, h->smp, ss, pinned, prefetch);
 }
 
 // ---- read-back of what the last gather decoded (tests and debugging) ----
@@ -455,6 +637,31 @@ int gvpm_upload_beams_dev(gvpm_context *h, const gvpm_photon_soa *beams, const f
   return uploadPhotonBeamsCommon(h, beams, end_n, true);
 }
 
+int gvpm_prefetch_beams(gvpm_context *h, const gvpm_photon_soa *beams, const float *end_n) {
+  CHECK_H(h);
+  return uploadPhotonBeamsCommon(h, beams, end_n, false, true);
+}
+int gvpm_prefetch_planes(gvpm_context *h, const gvpm_photon_soa *beams, const float *w1, const float *len1) {
+  CHECK_H(h);
+  return uploadPlanesCommon(h, beams, w1, len1, false, true);
+}
+int gvpm_upload_beams_linked(gvpm_context *h, const void *blob, size_t bytes, const uint32_t *end_n_oct) {
+  CHECK_H(h);
+  return uploadBeamsLinked(h, blob, bytes, end_n_oct, false);
+}
+int gvpm_prefetch_beams_linked(gvpm_context *h, const void *blob, size_t bytes, const uint32_t *end_n_oct) {
+  CHECK_H(h);
+  return uploadBeamsLinked(h, blob, bytes, end_n_oct, true);
+}
+int gvpm_upload_planes_linked(gvpm_context *h, const void *blob, size_t bytes, const float *w1, const float *len1) {
+  CHECK_H(h);
+  return uploadPlanesLinked(h, blob, bytes, w1, len1, false);
+}
+int gvpm_prefetch_planes_linked(gvpm_context *h, const void *blob, size_t bytes, const float *w1, const float *len1) {
+  CHECK_H(h);
+  return uploadPlanesLinked(h, blob, bytes, w1, len1, true);
+}
+
 int gvpm_upload_sensor(gvpm_context *h, const gvpm_sensor *sensor) {
   CHECK_H(h);
   if (!sensor) return fail(h, GVPM_ERR_INVALID_ARG, "null sensor");
@@ -511,6 +718,47 @@ int gvpm_upload_vpm_samples(gvpm_context *h, const gvpm_vpm_sample *samples, uin
 int gvpm_upload_vpm_samples_dev(gvpm_context *h, const gvpm_vpm_sample *samples, uint64_t n) {
   CHECK_H(h);
   return uploadSamplesCommon(h, samples, n, true);
+}
+
+int gvpm_prefetch_vpm_samples(gvpm_context *h, const gvpm_vpm_sample *samples, uint64_t n) {
+  CHECK_H(h);
+  return uploadSamplesCommon(h, samples, n, false, true);
+}
+int gvpm_upload_vpm_samples_packed(gvpm_context *h, const gvpm_vpm_run *runs, uint64_t n_runs, const float *rands, uint64_t n) {
+  CHECK_H(h);
+  return uploadSamplesPacked(h, runs, n_runs, rands, n, false);
+}
+int gvpm_prefetch_vpm_samples_packed(gvpm_context *h, const gvpm_vpm_run *runs, uint64_t n_runs, const float *rands, uint64_t n) {
+  CHECK_H(h);
+  return uploadSamplesPacked(h, runs, n_runs, rands, n, true);
+}
+
+int gvpm_download_beam_sides(gvpm_context *h, float *vec3_out, float *len1_out) {
+  CHECK_H(h);
+  if (!h->haveGathered) return fail(h, GVPM_ERR_STATE, "gvpm_download_beam_sides: no gather yet");
+  const bool planes = h->gatheredSide == gvpm_context::SIDE_PLANES;
+  if (!planes && h->gatheredSide != gvpm_context::SIDE_BEAMS)
+    return fail(h, GVPM_ERR_STATE, "gvpm_download_beam_sides: the last gather was neither G-Beams nor G-Planes");
+  const size_t n = (size_t)h->gatheredPh.n;
+  if (n && (!vec3_out || (planes && !len1_out))) return fail(h, GVPM_ERR_INVALID_ARG, "gvpm_download_beam_sides: null destination array");
+  if (n && !(planes ? h->gatheredW1 && h->gatheredLen1 : h->gatheredEndN != nullptr))
+    return fail(h, GVPM_ERR_STATE, "gvpm_download_beam_sides: that gather had no side arrays (it failed)");
+  if (int rc = syncAllStreams(h)) return rc;
+  if (n) HIP_TRY(h, hipMemcpy(vec3_out, planes ? h->gatheredW1 : h->gatheredEndN, n * 12, hipMemcpyDeviceToHost));
+  if (n && planes) HIP_TRY(h, hipMemcpy(len1_out, h->gatheredLen1, n * 4, hipMemcpyDeviceToHost));
+  return GVPM_OK;
+}
+
+int gvpm_download_vpm_samples(gvpm_context *h, gvpm_vpm_sample *dst, uint64_t cap, uint64_t *n) {
+  CHECK_H(h);
+  if (!h->haveGathered) return fail(h, GVPM_ERR_STATE, "gvpm_download_vpm_samples: no gather yet");
+  if (!h->gatheredVpm) return fail(h, GVPM_ERR_STATE, "gvpm_download_vpm_samples: the last gather was not a G-VPM one");
+  if (!n || (cap && !dst)) return fail(h, GVPM_ERR_INVALID_ARG, "gvpm_download_vpm_samples: null n or dst");
+  *n = h->gatheredNSamples;
+  const uint64_t m = std::min<uint64_t>(cap, h->gatheredNSamples);
+  if (int rc = syncAllStreams(h)) return rc;
+  if (m) HIP_TRY(h, hipMemcpy(dst, h->gatheredSamples, (size_t)m * sizeof(gvpm_vpm_sample), hipMemcpyDeviceToHost));
+  return GVPM_OK;
 }
 
 int gvpm_download_photons(gvpm_context *h, const gvpm_photon_soa *dst) {

@@ -36,6 +36,11 @@ SYMBOLS = [
     "gvpm_upload_sensor", "gvpm_pack_camera_beams_compact", "gvpm_unpack_camera_beams_compact",
     "gvpm_upload_camera_beams_compact", "gvpm_prefetch_camera_beams_compact", "gvpm_upload_bsdfs", "gvpm_gather_primal",
     "gvpm_download_photons", "gvpm_download_camera_beams",
+    "gvpm_prefetch_beams", "gvpm_prefetch_planes", "gvpm_prefetch_vpm_samples",
+    "gvpm_pack_normals_oct", "gvpm_unpack_normals_oct", "gvpm_pack_vpm_samples", "gvpm_unpack_vpm_samples",
+    "gvpm_upload_beams_linked", "gvpm_prefetch_beams_linked", "gvpm_upload_planes_linked", "gvpm_prefetch_planes_linked",
+    "gvpm_upload_vpm_samples_packed", "gvpm_prefetch_vpm_samples_packed",
+    "gvpm_download_beam_sides", "gvpm_download_vpm_samples",
 ]
 
 
@@ -131,6 +136,21 @@ def lib():
         L.gvpm_host_free.argtypes = [vp]
         L.gvpm_prefetch_photons.argtypes = [vp, C.POINTER(abi.PhotonSoA)]
         L.gvpm_prefetch_camera_beams.argtypes = [vp, vp, C.c_uint64]
+        L.gvpm_prefetch_beams.argtypes = [vp, C.POINTER(abi.PhotonSoA), vp]
+        L.gvpm_prefetch_planes.argtypes = [vp, C.POINTER(abi.PhotonSoA), vp, vp]
+        L.gvpm_prefetch_vpm_samples.argtypes = [vp, vp, C.c_uint64]
+        L.gvpm_pack_normals_oct.argtypes = [vp, C.c_uint64, vp]
+        L.gvpm_unpack_normals_oct.argtypes = [vp, C.c_uint64, vp]
+        L.gvpm_pack_vpm_samples.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
+        L.gvpm_unpack_vpm_samples.argtypes = [vp, C.c_uint64, vp, C.c_uint64, vp]
+        L.gvpm_upload_beams_linked.argtypes = [vp, vp, C.c_size_t, vp]
+        L.gvpm_prefetch_beams_linked.argtypes = [vp, vp, C.c_size_t, vp]
+        L.gvpm_upload_planes_linked.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.gvpm_prefetch_planes_linked.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.gvpm_upload_vpm_samples_packed.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
+        L.gvpm_prefetch_vpm_samples_packed.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
+        L.gvpm_download_beam_sides.argtypes = [vp, vp, vp]
+        L.gvpm_download_vpm_samples.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         _LIB = L
     return _LIB
 
@@ -184,6 +204,128 @@ class PinnedRays:
             self._p = C.c_void_p()
 
     __del__ = close
+
+
+class PinnedArray:
+    """A numpy array's bytes in pinned host memory (gvpm_host_alloc); `view` is a numpy view of the pinned copy."""
+
+    def __init__(self, arr):
+        arr = np.ascontiguousarray(arr)
+        self.nbytes = arr.nbytes
+        self._p = C.c_void_p()
+        rc = lib().gvpm_host_alloc(max(arr.nbytes, 64), C.byref(self._p))
+        if rc != 0:
+            raise GvpmError(rc, "gvpm_host_alloc failed")
+        self.view = np.frombuffer((C.c_char * max(arr.nbytes, 1)).from_address(self._p.value), np.uint8)[:arr.nbytes].view(arr.dtype).reshape(arr.shape)
+        self.view[...] = arr
+
+    @property
+    def ptr(self):
+        return self._p
+
+    def close(self):
+        if self._p:
+            self.view = None
+            lib().gvpm_host_free(self._p)
+            self._p = C.c_void_p()
+
+    __del__ = close
+
+
+class PinnedBeams:
+    """Photon beams (G-Beams: with end_n) or photon planes (G-Planes: with w1 and len1) in pinned host memory: the beam SoA in
+    one block (PinnedPhotons) and the side arrays beside it.  What gvpm_upload_beams / _planes leave in flight and
+    gvpm_prefetch_beams / _planes take.  With `table` (a MaterialTable) also the packed form: the beam records as one blob
+    of linked records and, for beams, the end normals as octahedral codes (gvpm_upload_beams_linked / _planes_linked)."""
+
+    def __init__(self, beams, end_n=None, w1=None, len1=None, table=None):
+        assert (end_n is None) != (w1 is None) and (w1 is None) == (len1 is None)
+        self.n = beams.n
+        self.planes = w1 is not None
+        self.photons = PinnedPhotons(max(beams.n, 1))   # (an empty set still names pinned memory)
+        if beams.n:
+            self.photons.fill(beams)
+        self.photons.soa.n = beams.n
+        self.soa = self.photons.soa
+        f32 = lambda a, shape: PinnedArray(np.ascontiguousarray(a, np.float32).reshape(shape))
+        self.end_n = None if self.planes else f32(end_n, (self.n, 3))
+        self.w1 = f32(w1, (self.n, 3)) if self.planes else None
+        self.len1 = f32(len1, (self.n,)) if self.planes else None
+        self.blob = self.end_n_oct = None
+        self.nbytes = self.n * 120 + (self.n * 16 if self.planes else self.n * 12)
+        if table is not None:
+            self.blob = PinnedArray(pack_photons_linked(beams, table))
+            self.packed_nbytes = self.blob.nbytes + self.n * 16
+            if not self.planes:
+                self.end_n_oct = PinnedArray(pack_normals_oct(end_n))
+                self.packed_nbytes = self.blob.nbytes + self.n * 4
+
+    def close(self):
+        for p in (self.photons, self.end_n, self.w1, self.len1, self.blob, self.end_n_oct):
+            if p is not None:
+                p.close()
+
+
+class PinnedSamples:
+    """G-VPM samples in pinned host memory, as records (gvpm_upload_vpm_samples / gvpm_prefetch_vpm_samples) and as runs +
+    rands (gvpm_upload_vpm_samples_packed / its prefetch twin)."""
+
+    def __init__(self, samples):
+        samples = np.ascontiguousarray(samples)
+        assert samples.dtype == abi.VPM_SAMPLE_DTYPE
+        self.n = samples.size
+        self.samples = PinnedArray(samples)
+        runs, rands = pack_vpm_samples(samples)
+        self.nruns = runs.size
+        self.runs, self.rands = PinnedArray(runs), PinnedArray(rands)
+        self.nbytes, self.packed_nbytes = samples.nbytes, runs.nbytes + rands.nbytes
+
+    def close(self):
+        for p in (self.samples, self.runs, self.rands):
+            p.close()
+
+
+def pack_normals_oct(normals):
+    """gvpm_pack_normals_oct: (n, 3) float32 -> n uint32 octahedral codes (the code of parent_n_oct; zero vector = GVPM_OCT_ZERO)"""
+    normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    codes = np.zeros(normals.shape[0], np.uint32)
+    rc = lib().gvpm_pack_normals_oct(normals.ctypes.data, codes.size, codes.ctypes.data)
+    if rc != 0:
+        raise GvpmError(rc, "gvpm_pack_normals_oct failed")
+    return codes
+
+
+def unpack_normals_oct(codes):
+    """gvpm_unpack_normals_oct: what the device makes of the codes, (n, 3) float32"""
+    codes = np.ascontiguousarray(codes, np.uint32)
+    out = np.zeros((codes.size, 3), np.float32)
+    rc = lib().gvpm_unpack_normals_oct(codes.ctypes.data, codes.size, out.ctypes.data)
+    if rc != 0:
+        raise GvpmError(rc, "gvpm_unpack_normals_oct failed")
+    return out
+
+
+def pack_vpm_samples(samples):
+    """gvpm_pack_vpm_samples: VPM_SAMPLE_DTYPE records -> (runs [VPM_RUN_DTYPE], rands [float32, one a sample])"""
+    samples = np.ascontiguousarray(samples)
+    assert samples.dtype == abi.VPM_SAMPLE_DTYPE
+    runs, rands = np.zeros(samples.size, abi.VPM_RUN_DTYPE), np.zeros(samples.size, np.float32)
+    nr = C.c_uint64(0)
+    rc = lib().gvpm_pack_vpm_samples(samples.ctypes.data, samples.size, runs.ctypes.data, runs.size, C.byref(nr), rands.ctypes.data)
+    if rc != 0:
+        raise GvpmError(rc, "gvpm_pack_vpm_samples failed (a sample with reserved != 0?)")
+    return runs[:nr.value].copy(), rands
+
+
+def unpack_vpm_samples(runs, rands):
+    """gvpm_unpack_vpm_samples: what the device makes of runs + rands; raises GvpmError for a malformed run list"""
+    runs, rands = np.ascontiguousarray(runs), np.ascontiguousarray(rands, np.float32)
+    assert runs.dtype == abi.VPM_RUN_DTYPE
+    out = np.zeros(rands.size, abi.VPM_SAMPLE_DTYPE)
+    rc = lib().gvpm_unpack_vpm_samples(runs.ctypes.data, runs.size, rands.ctypes.data, rands.size, out.ctypes.data)
+    if rc != 0:
+        raise GvpmError(rc, "gvpm_unpack_vpm_samples refused the run list")
+    return out
 
 
 class MaterialTable:
@@ -516,6 +658,69 @@ class Context:
         assert w1.size == 3 * beams.n and len1.size == beams.n
         self._check(lib().gvpm_upload_planes(self._h, C.byref(soa), w1.ctypes.data if beams.n else None,
                                              len1.ctypes.data if beams.n else None))
+
+    # beams / planes / G-VPM samples through the staging ring: pinned holders (PinnedBeams, PinnedSamples), packed forms
+    def upload_pinned_beams(self, pb, prefetch=False, packed=False):
+        """pb: PinnedBeams (beams or planes).  The copies are left in flight; prefetch: the set of the step AFTER the coming
+        gather (gvpm_prefetch_*); packed: the linked blob (+ octahedral end normals) instead of the SoA."""
+        L, h = lib(), self._h
+        if packed:
+            assert pb.blob is not None, "PinnedBeams was built without a material table"
+            if pb.planes:
+                f = L.gvpm_prefetch_planes_linked if prefetch else L.gvpm_upload_planes_linked
+                self._check(f(h, pb.blob.ptr, pb.blob.nbytes, pb.w1.ptr, pb.len1.ptr))
+            else:
+                f = L.gvpm_prefetch_beams_linked if prefetch else L.gvpm_upload_beams_linked
+                self._check(f(h, pb.blob.ptr, pb.blob.nbytes, pb.end_n_oct.ptr))
+        elif pb.planes:
+            f = L.gvpm_prefetch_planes if prefetch else L.gvpm_upload_planes
+            self._check(f(h, C.byref(pb.soa), pb.w1.ptr, pb.len1.ptr))
+        else:
+            f = L.gvpm_prefetch_beams if prefetch else L.gvpm_upload_beams
+            self._check(f(h, C.byref(pb.soa), pb.end_n.ptr))
+
+    def upload_beams_linked(self, blob, end_n_oct):
+        """blob: gvpm_pack_photons_linked of the beam SoA; end_n_oct: pack_normals_oct(end_n)"""
+        blob, end_n_oct = np.ascontiguousarray(blob), np.ascontiguousarray(end_n_oct, np.uint32)
+        self._check(lib().gvpm_upload_beams_linked(self._h, blob.ctypes.data, blob.size, end_n_oct.ctypes.data if end_n_oct.size else None))
+
+    def upload_planes_linked(self, blob, w1, len1):
+        blob = np.ascontiguousarray(blob)
+        w1, len1 = np.ascontiguousarray(w1, np.float32), np.ascontiguousarray(len1, np.float32)
+        assert w1.size == 3 * len1.size
+        self._check(lib().gvpm_upload_planes_linked(self._h, blob.ctypes.data, blob.size, w1.ctypes.data if len1.size else None,
+                                                    len1.ctypes.data if len1.size else None))
+
+    def upload_vpm_samples_packed(self, runs, rands):
+        runs, rands = np.ascontiguousarray(runs), np.ascontiguousarray(rands, np.float32)
+        assert runs.dtype == abi.VPM_RUN_DTYPE
+        self._check(lib().gvpm_upload_vpm_samples_packed(self._h, runs.ctypes.data if runs.size else None, runs.size,
+                                                         rands.ctypes.data if rands.size else None, rands.size))
+
+    def upload_pinned_vpm_samples(self, ps, prefetch=False, packed=False):
+        """ps: PinnedSamples; as upload_pinned_beams"""
+        L, h = lib(), self._h
+        if packed:
+            f = L.gvpm_prefetch_vpm_samples_packed if prefetch else L.gvpm_upload_vpm_samples_packed
+            self._check(f(h, ps.runs.ptr, ps.nruns, ps.rands.ptr, ps.n))
+        else:
+            f = L.gvpm_prefetch_vpm_samples if prefetch else L.gvpm_upload_vpm_samples
+            self._check(f(h, ps.samples.ptr, ps.n))
+
+    def download_beam_sides(self, n):
+        """the side arrays the last gather read: end_n (n, 3) after a G-Beams gather, (w1 (n, 3), len1 (n,)) after a G-Planes one"""
+        v, l1 = np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        self._check(lib().gvpm_download_beam_sides(self._h, v.ctypes.data, l1.ctypes.data))
+        return (v, l1) if self.params.vol_technique == abi.GVPM_VOL_PLANE0D else v
+
+    def download_vpm_samples(self):
+        """the G-VPM samples the last gather read (VPM_SAMPLE_DTYPE)"""
+        n = C.c_uint64(0)
+        self._check(lib().gvpm_download_vpm_samples(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, abi.VPM_SAMPLE_DTYPE)
+        if n.value:
+            self._check(lib().gvpm_download_vpm_samples(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out
 
     def upload_beams_dev(self, soa, end_n_dev_ptr):
         """soa: abi.PhotonSoA of device addresses (photon beams); end_n_dev_ptr: 3 floats per beam, device."""

@@ -544,6 +544,17 @@ int gvpm_host_free(void *p);
  *   upload(1); for N: prefetch(N+1); gather(N).                                                                     */
 int gvpm_prefetch_photons(gvpm_context *h, const gvpm_photon_soa *photons);
 int gvpm_prefetch_camera_beams(gvpm_context *h, const gvpm_camera_ray *rays, uint64_t n_sets);
+/* The same for the other techniques' inputs: photon beams with their end normals (G-Beams), photon planes with their second
+ * edges (G-Planes), the camera samples of G-VPM.  The side arrays (end_n; w1, len1) travel in the staging slot of their beam
+ * records and the samples in a ring of three slots of their own, all copied on the copy stream: an upload from pinned memory
+ * is left in flight, one from pageable memory is complete when the call returns.  A prefetched set becomes current when the
+ * coming gvpm_gather or gvpm_gather_primal returns.  One pending set per kind (beams, planes and photons are ONE kind: they
+ * share the photon slots); at most 2^24 - 1 beams or planes (G-Beams' beam index).
+ * Lifetime of a pinned buffer handed to ANY upload or prefetch, side arrays and samples included: untouched until the gather
+ * that consumes it has returned, or gvpm_synchronize has.                                                              */
+int gvpm_prefetch_beams(gvpm_context *h, const gvpm_photon_soa *beams, const float *end_n);
+int gvpm_prefetch_planes(gvpm_context *h, const gvpm_photon_soa *beams, const float *w1, const float *len1);
+int gvpm_prefetch_vpm_samples(gvpm_context *h, const gvpm_vpm_sample *samples, uint64_t n);
 
 /* ---- packed uploads (round 3) ----------------------------------------------*/
 /* The SoA entry points above move 120 bytes a photon and 320 a beam set over PCIe -- at C2 2.9 times the duration of the
@@ -733,6 +744,45 @@ int gvpm_upload_camera_beams_compact(gvpm_context *h, const gvpm_beam_set_compac
 int gvpm_prefetch_camera_beams_compact(gvpm_context *h, const gvpm_beam_set_compact *compact, uint64_t n_compact,
                                        const gvpm_beam_set_packed *full, uint64_t n_full);
 
+/* ---- packed photon beams, photon planes and G-VPM samples ------------------------------------------------------------*/
+/* Photon beams and planes are photon SoAs re-read (gvpm_upload_beams): gvpm_pack_photons_linked packs them as they stand --
+ * it verifies every short record against the source, the gathers read `path_id & 1` only, and a beam's wi IS
+ * normalize(parent_pos - pos), which the decoder derives.  What a blob means is gvpm_unpack_photons_linked's.
+ *   beams  -- the end normals travel as one octahedral code per beam (the code of parent_n_oct: 2 x snorm16; 0x80008000 is
+ *             the zero vector a medium end vertex carries; axis-aligned normals are exact, others within 4.8e-5 rad:
+ *             gvpm_pack_normals_oct picks the nearest of the four codes around a normal, 4.3e-5 rad at worst).  What
+ *             the codes mean is DEFINED by gvpm_unpack_normals_oct; the device decodes with the same arithmetic.
+ *   planes -- w1 and len1 stay fp32 (lossless); only the beam records are packed.
+ *   G-VPM samples -- the samples of a pixel are consecutive and share `set` and `pdf_sel`: they travel as RUNS plus one
+ *             `float rand` per sample.  Sample first + k (k < count) of a run is {set, rands[first + k], pdf_sel, 0}; the
+ *             runs are contiguous from sample 0 (first of run r + 1 = first + count of run r), none is empty, and their
+ *             counts sum to n.  Lossless; 4 + 16 / nb_camera_samples bytes a sample where a pixel has one medium edge.
+ *             gvpm_pack_vpm_samples forms maximal runs of equal `set` and bit-equal `pdf_sel` (runs_cap entries of room:
+ *             n always suffice) and refuses a sample whose `reserved` is not 0; gvpm_unpack_vpm_samples DEFINES the
+ *             meaning and refuses a run list that breaks the rules above; the uploads run the same check on the host
+ *             before anything is copied (GVPM_ERR_INVALID_ARG: the previous samples stay in force).
+ * The prefetch twins take pinned memory only, as gvpm_prefetch_photons.                                                  */
+typedef struct gvpm_vpm_run { /* 16 bytes */
+  uint32_t set;
+  float pdf_sel;
+  uint32_t first;             /* index of the run's first sample                                                          */
+  uint32_t count;
+} gvpm_vpm_run;
+int gvpm_pack_normals_oct(const float *normals, uint64_t n, uint32_t *codes);     /* 3 floats -> 1 code, n times            */
+int gvpm_unpack_normals_oct(const uint32_t *codes, uint64_t n, float *normals);
+int gvpm_pack_vpm_samples(const gvpm_vpm_sample *samples, uint64_t n, gvpm_vpm_run *runs, uint64_t runs_cap,
+                          uint64_t *n_runs, float *rands);
+int gvpm_unpack_vpm_samples(const gvpm_vpm_run *runs, uint64_t n_runs, const float *rands, uint64_t n,
+                            gvpm_vpm_sample *dst);
+int gvpm_upload_beams_linked(gvpm_context *h, const void *blob, size_t bytes, const uint32_t *end_n_oct);
+int gvpm_prefetch_beams_linked(gvpm_context *h, const void *blob, size_t bytes, const uint32_t *end_n_oct);
+int gvpm_upload_planes_linked(gvpm_context *h, const void *blob, size_t bytes, const float *w1, const float *len1);
+int gvpm_prefetch_planes_linked(gvpm_context *h, const void *blob, size_t bytes, const float *w1, const float *len1);
+int gvpm_upload_vpm_samples_packed(gvpm_context *h, const gvpm_vpm_run *runs, uint64_t n_runs, const float *rands,
+                                   uint64_t n);
+int gvpm_prefetch_vpm_samples_packed(gvpm_context *h, const gvpm_vpm_run *runs, uint64_t n_runs, const float *rands,
+                                     uint64_t n);
+
 /* ---- read-back of decoded inputs (for tests and debugging; not part of a render loop) --------------------------------*/
 /* What the LAST gather read, as the device decoded it, before the next upload into the same staging slot.  Both wait for
  * every stream of the handle, then copy.  GVPM_ERR_STATE before the first gather.
@@ -742,6 +792,13 @@ int gvpm_prefetch_camera_beams_compact(gvpm_context *h, const gvpm_beam_set_comp
  *   ones: new_index of gvpm_pack_camera_beams_compact); min(cap, *n) sets are copied, *n = the gather's set count.       */
 int gvpm_download_photons(gvpm_context *h, const gvpm_photon_soa *dst);
 int gvpm_download_camera_beams(gvpm_context *h, gvpm_camera_ray *dst, uint64_t cap, uint64_t *n);
+/* gvpm_download_beam_sides: the side arrays of that gather's beams, one entry per photon of gvpm_download_photons --
+ *   after a G-Beams gather the end normals into vec3_out (3 floats a beam; len1_out is not touched and may be NULL), after
+ *   a G-Planes gather w1 into vec3_out and len1 into len1_out.  GVPM_ERR_STATE after a gather of another technique.
+ * gvpm_download_vpm_samples: the G-VPM samples; min(cap, *n) are copied, *n = the gather's sample count (GVPM_ERR_STATE
+ *   when the last gather was not a G-VPM one).                                                                           */
+int gvpm_download_beam_sides(gvpm_context *h, float *vec3_out, float *len1_out);
+int gvpm_download_vpm_samples(gvpm_context *h, gvpm_vpm_sample *dst, uint64_t cap, uint64_t *n);
 
 /* ---- manifold shifts through the host (first slice) ----------------------------------------*/
 /* A photon whose shift type is 3 (EManifoldShift: a specular chain between the photon and the vertex it can be re-connected
