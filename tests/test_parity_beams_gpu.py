@@ -6,6 +6,7 @@ import cases
 import oracle_lib as O
 from gvpm_amd import abi, hip
 from test_oracle_beams import make_beam_case, TECHS
+from entry_parity import assert_entry_parity
 from test_parity_gpu import l2, TOL
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +19,7 @@ def device_beams(c, p=None, rays=None, iters=1, exact=True):
     ctx.upload_scene(*c.tris)
     ctx.upload_medium(c.m)
     cases.upload_bsdfs(ctx, c)
-    ref = None
+    ref = r32 = None
     total = {k: 0 for k in SHIFT_COUNTERS + ("evaluations",)}
     for it in range(1, iters + 1):
         if it == 1:
@@ -31,6 +32,7 @@ def device_beams(c, p=None, rays=None, iters=1, exact=True):
         ctx.upload_camera_beams(r)
         ctx.gather(it, nb)
         ref, cnt, _ = O.gather_beams(p, c.m, c.tris, beams, en, r, rad, it, nb, 64, accum=ref)
+        r32, _, _ = O.gather_beams(p, c.m, c.tris, beams, en, r, rad, it, nb, 32, accum=r32)
         for k in total:
             total[k] += cnt[k]
     acc = ctx.download_accum()
@@ -48,6 +50,8 @@ def device_beams(c, p=None, rays=None, iters=1, exact=True):
     for k in SHIFT_COUNTERS:
         assert abs(st[k] - total[k]) <= (0 if exact else 2), (k, st, total)
     assert l2(acc, ref, lum) < 2e-4   # (measured 6e-6 .. 6e-5; SURVEY's bar is 1e-3)
+    # per entry, in units of the reference's own fp32 noise on these inputs (entry_parity.py): zeros and bulk
+    assert_entry_parity(acc, ref, r32, lum, tail=False, inputs=False)
     rfilm = O.assemble(ref, iters, True)
     for a, b in zip(film, rfilm):
         assert l2(a, b, lum) < 2e-4

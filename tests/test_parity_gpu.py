@@ -5,7 +5,10 @@ Bars (BASELINE.md "Parity bar"):
   * evaluation count == oracle count exactly (the device evaluates the reference hit
     predicate in fp64 without contraction);
   * per-pixel L2 of the 27 accumulators / throughput / dx / dy against the fp64 oracle,
-    normalised by the mean reference luminance, < 1e-3 (measured ~1e-6; asserted < 1e-4).
+    normalised by the mean reference luminance, < 1e-3 (measured ~1e-6; asserted < 1e-4);
+  * per entry of the 27 accumulators, where the device sees the oracle's inputs bit for bit (exact=True): exactly 0 wherever
+    the fp64 oracle is, and p50 / p90 / p99 of the relative error within 4x / 4x / 8x of the fp32 oracle's own on the same
+    inputs (entry_parity.py A and B; the tail bar C on the admitted inputs of test_entry_parity_gpu.py).
 """
 import os
 
@@ -14,6 +17,7 @@ import pytest
 
 import cases
 import oracle_lib as O
+from entry_parity import assert_entry_parity
 from gvpm_amd import abi, hip
 
 pytestmark = pytest.mark.gpu
@@ -67,6 +71,12 @@ def check(c, p=None, rays=None, ph=None, use_accel=False, exact=True, **kw):
         assert abs(st[k] - cnt[k]) <= (0 if exact else max(2, 2e-6 * 4 * cnt["evaluations"])), (k, st, cnt)
     err = l2(acc, ref, lum)
     assert err < TOL, err
+    if exact:
+        # per entry, in units of the reference's own fp32 noise on these inputs (entry_parity.py): zeros and bulk; the tail bar
+        # needs admitted inputs (entry_cases.py)
+        r32, _, _ = O.gather_bre(p, c.m, c.tris, c.ph if ph is None else ph, c.rays if rays is None else rays, c.r, c.it, c.nb, 32,
+                                 use_accel=use_accel)
+        assert_entry_parity(acc, ref, r32, lum, tail=False, inputs=False)
     rthr, rdx, rdy = O.assemble(ref, c.it, True)
     for a, b in zip(film, (rthr, rdx, rdy)):
         assert l2(a, b, lum) < TOL

@@ -6,6 +6,7 @@ import cases
 import oracle_lib as O
 from gvpm_amd import abi, hip
 from test_oracle_planes import make_plane_case
+from entry_parity import assert_entry_parity
 from test_parity_gpu import l2
 
 pytestmark = pytest.mark.gpu
@@ -16,7 +17,7 @@ def device_planes(c, p=None, rays=None, iters=1, exact=True):
     ctx = hip.Context(p, device=0)
     ctx.upload_scene(*c.tris)
     ctx.upload_medium(c.m)
-    ref = None
+    ref = r32 = None
     total = dict(evaluations=0, diffuse_shifts=0, failed_shifts=0)
     for it in range(1, iters + 1):
         if it == 1:
@@ -28,6 +29,7 @@ def device_planes(c, p=None, rays=None, iters=1, exact=True):
         ctx.upload_camera_beams(r)
         ctx.gather(it, nb)
         ref, cnt, _ = O.gather_planes(p, c.m, c.tris, beams, w1, l1, r, it, nb, 64, accum=ref)
+        r32, _, _ = O.gather_planes(p, c.m, c.tris, beams, w1, l1, r, it, nb, 32, accum=r32)
         for k in total:
             total[k] += cnt[k]
     acc = ctx.download_accum()
@@ -41,6 +43,8 @@ def device_planes(c, p=None, rays=None, iters=1, exact=True):
     assert abs(st["diffuse_shifts"] - total["diffuse_shifts"]) <= tol and abs(st["failed_shifts"] - total["failed_shifts"]) <= tol, (st, total)
     assert st["null_shifts"] == 0
     assert l2(acc, ref, lum) < 1e-5
+    # per entry, in units of the reference's own fp32 noise on these inputs (entry_parity.py): zeros and bulk
+    assert_entry_parity(acc, ref, r32, lum, tail=False, inputs=False)
     rfilm = O.assemble(ref, iters, True)
     for a, b in zip(film, rfilm):
         assert l2(a, b, lum) < 1e-5

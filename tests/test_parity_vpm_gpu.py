@@ -6,6 +6,7 @@ import cases
 import oracle_lib as O
 from gvpm_amd import abi, hip
 from test_oracle_vpm import make_vpm_case
+from entry_parity import assert_entry_parity
 from test_parity_gpu import l2, TOL
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +19,7 @@ def device_vpm(c, iters=1, p=None, rays=None, exact=True, nph=None):
     ctx.upload_scene(*c.tris)
     ctx.upload_medium(c.m)
     cases.upload_bsdfs(ctx, c)
-    ref = sv = nv = None
+    ref = sv = nv = r32 = sv32 = nv32 = None
     total = 0
     shifts = {k: 0 for k in ("null_shifts", "diffuse_shifts", "failed_shifts")}
     emitted = 0
@@ -35,6 +36,7 @@ def device_vpm(c, iters=1, p=None, rays=None, exact=True, nph=None):
         emitted += nb
         ref, sv, nv, cnt, _ = O.gather_vpm(p, c.m, c.tris, ph, r, smp, 64, use_accel=False, accum=ref, scale_vol=sv,
                                            n_vol=nv)
+        r32, sv32, nv32, _, _ = O.gather_vpm(p, c.m, c.tris, ph, r, smp, 32, use_accel=False, accum=r32, scale_vol=sv32, n_vol=nv32)
         total += cnt["evaluations"]
         for k in shifts:
             shifts[k] += cnt[k]
@@ -48,6 +50,8 @@ def device_vpm(c, iters=1, p=None, rays=None, exact=True, nph=None):
     for k in shifts:
         assert abs(st[k] - shifts[k]) <= (0 if exact else max(2, 2e-6 * 4 * total)), (k, st, shifts)
     assert l2(acc, ref, lum) < TOL
+    # per entry, in units of the reference's own fp32 noise on these inputs (entry_parity.py): zeros and bulk
+    assert_entry_parity(acc, ref, r32, lum, tail=False, inputs=False)
     assert np.allclose(dsv, sv, rtol=1e-6) and np.allclose(dnv, nv, rtol=1e-6)
     rfilm = O.assemble(ref, iters, True, total_emitted=emitted)
     for a, b in zip(film, rfilm):
