@@ -64,7 +64,7 @@ void launch_build_chain(ChainArgs c, const GatherArgs &a, const gvpm_photon_soa 
 void launch_apply_host_shifts(const GatherArgs &a, const gvpm_host_shift *results, uint32_t n, hipStream_t s);
 void launch_plan_bre(const GatherArgs &a, int beamsPerWave, uint32_t ntiles, uint32_t target, uint4 *items,
                      uint32_t *itemCount, uint2 *itemOff, uint32_t *blockTotal, uint32_t itemCap, hipStream_t stream);
-// units / unitCtl / unitCap: the evaluation's work units (gather_bre.hip, EVAL_UNIT) -- two lists of unitCap entries, their
+// units / unitCtl / unitCap: the evaluation's work units (gather_bre_common.h, EVAL_UNIT) -- two lists of unitCap entries, their
 // lengths in unitCtl[0..1] (zero on entry); null: the evaluation takes whole items
 uint32_t eval_unit_pairs();
 void launch_traverse_bre(const GatherArgs &a, int beamsPerWave, const uint4 *items, const uint2 *itemOff,

@@ -128,7 +128,7 @@ static_assert(sizeof(ExEntry) == 512, "ExEntry is 512 bytes");
 // per gather where the uploaded BSDF table holds a GVPM_BSDF_MIXTURE head: G-BRE then launches evaluate_bre_mix_kernel
 #define GVPM_TABLE_HAS_MIXTURE 256
 // ... and this one at gvpm_create by GVPM_EVAL_GENERIC=1: G-BRE launches the evaluation kernel that reads the configuration from its
-// arguments whatever the configuration is (gather_bre.hip, headlineConfig)
+// arguments whatever the configuration is (gather_bre_eval.hip, headlineConfig)
 #define GVPM_EVAL_FORCE_GENERIC 512
 struct GatherArgs {
   // photons

@@ -149,7 +149,7 @@ int queueGather(BreStep &s, uint32_t blocks, uint32_t nItems, bool optimistic, b
   if (rc == GVPM_OK) rc = nextEvents(h, &s.evEval, 0);
   if (rc != GVPM_OK) return rc;
   const hipStream_t ts = !h->pipeline ? h->stream : (h->travStream ? h->streamC : h->streamB), es = h->stream;
-  // the evaluation's work units (gather_bre.hip, EVAL_UNIT): an item yields at most staged x beams pairs, i.e. at most
+  // the evaluation's work units (gather_bre_common.h, EVAL_UNIT): an item yields at most staged x beams pairs, i.e. at most
   // blocks_i * 64 / unit + 1 parts; their counters are queueCtl[5..6] (zeroed with the queue heads)
   uint2 *units = nullptr;
   uint32_t unitCap = 0;

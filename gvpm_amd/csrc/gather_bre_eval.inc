@@ -1,4 +1,4 @@
-// The G-BRE evaluation kernel, included by gather_bre.hip once per form: GVPM_EVAL_KERNEL = its name, GVPM_EVAL_MIX = whether it
+// The G-BRE evaluation kernel, included by gather_bre_eval.hip once per form: GVPM_EVAL_KERNEL = its name, GVPM_EVAL_MIX = whether it
 // evaluates mixture parents (GVPM_BSDF_MIXTURE; parent_bsdf.h, glossyParentEval<MIX>).  The text is the kernel's own, unchanged: as a
 // __forceinline__ body shared by two __global__ wrappers every instantiation's assembly moved (NOTEBOOK.md, "Mixture parents").
 // CFG (shift_device.h): EvalCfgGeneric reads the integrator configuration from a.cfg; a fixed one compiles its dead paths out.

@@ -40,7 +40,7 @@ void fillArgs(const gvpm_context *h, GatherArgs &a, float r) {
   a.med.g = h->medium.g;
   a.med.msw = h->medium.medium_sampling_weight;
   a.cfg = h->cfg;
-  if (h->bsdfMixtures) a.cfg.reserved[0] |= GVPM_TABLE_HAS_MIXTURE;  // (gather_bre.hip, launch_evaluate_bre)
+  if (h->bsdfMixtures) a.cfg.reserved[0] |= GVPM_TABLE_HAS_MIXTURE;  // (gather_bre_eval.hip, launch_evaluate_bre)
   a.radius = r;
   a.iter = h->iter.p;
   a.stats = h->stats.p;

@@ -95,7 +95,7 @@ int gvpm_create(const gvpm_params *params, int device, gvpm_context **out) {
   if (const char *e = getenv("GVPM_DEBUG_FLAGS")) h->cfg.reserved[0] = atoi(e);
   if (const char *e = getenv("GVPM_TRAV_PREFILTER"))
     if (!atoi(e)) h->cfg.reserved[0] |= 128;  // (gather_bre.hip: traverse_bre_kernel's tile cylinder)
-  if (const char *e = getenv("GVPM_RECORD_PREFETCH")) h->cfg.reserved[0] |= atoi(e) ? 64 : 32;  // (gather_bre.hip: launch_evaluate_bre)
+  if (const char *e = getenv("GVPM_RECORD_PREFETCH")) h->cfg.reserved[0] |= atoi(e) ? 64 : 32;  // (gather_bre_eval.hip: launch_evaluate_bre)
   h->cfg.reserved[1] = 0;  // slab layers per step (0 = default)
   if (const char *e = getenv("GVPM_SLAB_LAYERS")) h->cfg.reserved[1] = atoi(e);
   h->cfg.reserved[2] = 0;  // slab layers per step when x is the major axis (0 = default)
@@ -143,7 +143,7 @@ int gvpm_create(const gvpm_params *params, int device, gvpm_context **out) {
   if (const char *e = getenv("GVPM_PLAN_GROUPS")) h->planGroups = atoi(e) != 0;
   if (const char *e = getenv("GVPM_EVAL_UNITS")) h->evalUnits = atoi(e) != 0;
   if (const char *e = getenv("GVPM_EVAL_GENERIC"))
-    if (atoi(e)) h->cfg.reserved[0] |= GVPM_EVAL_FORCE_GENERIC;  // (gather_bre.hip: launchEvaluate)
+    if (atoi(e)) h->cfg.reserved[0] |= GVPM_EVAL_FORCE_GENERIC;  // (gather_bre_eval.hip: launchEvaluate)
   if (const char *e = getenv("GVPM_OPTIMISTIC")) h->optimistic = atoi(e) != 0;
   if (const char *e = getenv("GVPM_OPTIMISTIC_REFUSE")) h->optRefuseEvery = (uint32_t)std::max(0, atoi(e));
   if (const char *e = getenv("GVPM_CLIP_GRID")) h->clipGrid = atoi(e) != 0;

@@ -278,7 +278,7 @@ __device__ __forceinline__ bool mixtureEval(const GatherArgs &a, uint32_t bi, f3
 // False: no such entry (a failed shift).
 // MIX: the kernel evaluates mixture entries (GVPM_BSDF_MIXTURE), dispatched LAST.  Everywhere but in the G-BRE evaluation, whose
 // kernels exist in both forms: the one without reads such an entry as no kind, and is launched only where the table holds none
-// (gather_bre.hip, launch_evaluate_bre) -- with the arm inlined the kernel of a plain benchmark run spilled 15 VGPRs where it spills 7.
+// (gather_bre_eval.hip, launch_evaluate_bre) -- with the arm inlined the kernel of a plain benchmark run spilled 15 VGPRs where it spills 7.
 // state (optional out, round 5): bit 0 -- the pdf is POSITIVE in double precision although it underflowed here (the
 // specular component of a Phong wall alone, exponent ~1000: alpha^e leaves fp32 below alpha ~ 0.94 and fp64 only below ~0.6;
 // with pdf == 0 the reference fails the shift, with a positive one -- however small -- it succeeds, with weight 1 and a

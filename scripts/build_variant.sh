@@ -9,8 +9,10 @@ out=$root/build/variants
 mkdir -p $out
 make -s -C $cs
 obj=$out/${file%.hip}_$name.o
+# (the unit's own flags, as the Makefile has them, come before the variant's: a later -fslp-vectorize overrides an earlier -fno-)
+unit=$(make -s --no-print-directory -C $cs unit-flags-${file%.hip})
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -fno-hip-fp32-correctly-rounded-divide-sqrt \
-  -Wno-unused-function -Wno-unused-variable -Wno-unused-result "$@" -I$cs -c $cs/$file -o $obj
+  -Wno-unused-function -Wno-unused-variable -Wno-unused-result $unit "$@" -I$cs -c $cs/$file -o $obj
 # the library's objects as the Makefile lists them, the one of FILE.hip replaced
 objs=""
 for o in $(make -s --no-print-directory -C $cs print-objs); do

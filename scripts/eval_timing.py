@@ -1,5 +1,5 @@
 """Probe: where the waves of evaluate_bre_kernel spend their time (shader-clock ticks summed over waves).
-Needs the -DGVPM_EVAL_TIMING variant: bash scripts/build_variant.sh timing gather_bre.hip -DGVPM_EVAL_TIMING
+Needs the -DGVPM_EVAL_TIMING variant: bash scripts/build_variant.sh timing gather_bre_eval.hip -DGVPM_EVAL_TIMING
   python scripts/eval_timing.py [bench args]"""
 import ctypes
 import os
