@@ -366,3 +366,12 @@ class DevgenScene(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32), ("seed", C.c_uint32), ("camera_inside", C.c_int32),
                 ("max_depth", C.c_int32), ("rr_depth", C.c_int32), ("min_depth", C.c_int32),
                 ("camera_sphere", C.c_double), ("cam_to_world", C.c_double * 9)]
+
+
+class DevgenMaterial(C.Structure):
+    """gvpm_devgen_material: what a material carries beyond kind and albedo (gvpm_devgen_create_ex)."""
+    _fields_ = [("spec", C.c_double * 3), ("exponent", C.c_double), ("spec_weight", C.c_double),
+                ("eta", C.c_double * 3), ("k", C.c_double * 3), ("coat_eta", C.c_double), ("fdr", C.c_double),
+                ("alpha_v", C.c_double), ("tangent", C.c_double * 3), ("mix_w", C.c_double * 2),
+                ("rtrans", C.c_void_p), ("bsdf", C.c_int32), ("distribution", C.c_int32), ("nonlinear", C.c_int32),
+                ("child", C.c_int32 * 2), ("reserved", C.c_int32 * 3)]

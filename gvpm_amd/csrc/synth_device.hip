@@ -18,6 +18,12 @@
 #include "../host/synth_core.h"
 #include "device_types.h"
 #include "scan_sort.h"
+#include "synth_device_launch.h"
+
+// the walk and camera-beam kernels of the closed set (Lambertian / index-matched / mirror) and their launchers; the same text with
+// the glossy materials compiled in is synth_device_glossy.hip's
+#define GVPM_SYNTH_K(name) GVPM_SYNTH_PLAIN(name)
+#include "synth_walk_kernels.inc"
 
 namespace gvpm {
 
@@ -48,106 +54,6 @@ struct PhotonOut {
   uint32_t *flags, *pathId;
   float *endN;
 };
-
-// the sinks of flattenPath / flattenBeams (synth_core.h): the count pass keeps a number, the write pass stores each record
-// where it belongs -- neither holds the path's records in (scratch) memory
-struct CountSink {
-  int n;
-  __device__ CountSink() : n(0) {}
-  __device__ void clear() { n = 0; }
-  __device__ bool empty() const { return n == 0; }
-  __device__ void push_back(const PhotonRec &) {
-    if (n < GVPM_SYNTH_MAXV) ++n;
-  }
-};
-// The walk runs ONCE (round 3; it ran twice: count, then write): its records are parked at a slot that depends on the path
-// alone -- path k, record n at (k * stride + n) -- and a copy kernel moves them to their place in the output once the
-// scans have said where that is.  32 words a record; with 288 GB of HBM the 1-2 GB of parking space are affordable, a
-// second walk of 0.85 M light paths in fp64 (1.5 ms) was not.
-constexpr int PARK_WORDS = 32;
-struct ParkSink {
-  float *park;  // this path's slots
-  int n, stride;
-  __device__ void clear() { n = 0; }
-  __device__ bool empty() const { return n == 0; }
-  __device__ void push_back(const PhotonRec &r) {
-    if (n >= stride) return;
-    float *d = park + (size_t)n * PARK_WORDS;
-    ++n;
-    const V3 v[9] = {r.pos, r.wi, r.flux, r.parentPos, r.parentN, r.prefixW, r.parentScat, r.parentWi, r.endN};
-#pragma unroll
-    for (int a = 0; a < 9; ++a) {
-      d[3 * a] = (float)v[a].x;
-      d[3 * a + 1] = (float)v[a].y;
-      d[3 * a + 2] = (float)v[a].z;
-    }
-    d[27] = r.parentPdf;
-    d[28] = r.edgePdf;
-    d[29] = r.parentRR;
-    d[30] = r.parentG;
-    d[31] = __uint_as_float(r.flags);
-  }
-};
-
-// A wave owns `chunk` consecutive paths of the batch and its lanes REFILL: a lane whose path has ended takes the wave's next
-// path while its neighbours walk on (walkBegin / walkStep, synth_core.h).  With one path per lane a wave ran until its
-// longest path ended -- twelve bounces with the mean near five: less than half of the lane-steps did work.  Where a path's
-// records are parked depends on the path alone, so which lane walks it changes nothing.
-template <bool BEAMS>
-__device__ __forceinline__ void walkChunk(const SceneView &sc, int iteration, uint64_t base, uint32_t k0, uint32_t k1, float *park,
-                                          int stride, uint32_t *counts, uint32_t *counted, uint32_t *nonEmpty) {
-  const int lane = threadIdx.x & 63;
-  ParkSink recs;
-  recs.park = park;
-  recs.stride = stride;
-  recs.n = 0;
-  StreamPath<ParkSink, BEAMS> path(sc, recs);
-  Philox rng(sc.seed, 0x11ffu, (uint32_t)iteration, 0u, 0u);
-  V3 throughput(1.0);
-  uint32_t next = k0;  // wave-uniform
-  uint32_t k = 0;
-  int i = 0;
-  bool active = false;
-  for (;;) {
-    // refill: the idle lanes take the next paths, in lane order
-    const unsigned long long idle = __ballot(!active);
-    if (idle && next < k1) {
-      const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-      if (!active && next + rank < k1) {
-        k = next + rank;
-        const uint64_t idx = base + k;
-        rng = Philox(sc.seed, 0x11ffu, (uint32_t)iteration, (uint32_t)idx, (uint32_t)(idx >> 32));
-        recs.park = park + (size_t)k * stride * PARK_WORDS;
-        walkBegin(sc, rng, path, throughput);
-        i = 1;
-        active = true;
-      }
-      next = min(k1, next + (uint32_t)__popcll(idle));
-    }
-    if (!__ballot(active)) break;
-    if (active) {
-      if (i >= sc.maxDepth || !walkStep(sc, rng, path, throughput, i)) {
-        const bool c = path.finish();
-        counts[k] = (uint32_t)recs.n;
-        counted[k] = c ? 1u : 0u;
-        nonEmpty[k] = recs.n ? 1u : 0u;
-        active = false;
-      } else {
-        ++i;
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(64) void synth_walk_kernel(SceneView sc, int iteration, uint64_t base, uint32_t m, uint32_t chunk, int beams,
-                                                        float *park, int stride, uint32_t *counts, uint32_t *counted,
-                                                        uint32_t *nonEmpty) {
-  const uint32_t k0 = blockIdx.x * chunk;
-  if (k0 >= m) return;
-  const uint32_t k1 = min(m, k0 + chunk);
-  if (beams) walkChunk<true>(sc, iteration, base, k0, k1, park, stride, counts, counted, nonEmpty);
-  else walkChunk<false>(sc, iteration, base, k0, k1, park, stride, counts, counted, nonEmpty);
-}
 
 // ctl: [0] photons stored before this batch, [1] paths counted before, [2] paths with photons before,
 //      [3] (out) paths of this batch that the host loop would have processed
@@ -201,43 +107,11 @@ __global__ __launch_bounds__(256) void synth_place_kernel(const float *__restric
   o.pathId[i] = ctl[2] + neOffs[k];
 }
 
-// ---- camera beams ----
-__device__ __forceinline__ bool ownedPixel(const SceneView &sc, uint32_t p, int tileMod, int tileRem, int &px, int &py) {
-  px = (int)(p % (uint32_t)sc.width);
-  py = (int)(p / (uint32_t)sc.width);
-  const int tilesX = (sc.width + 3) / 4;
-  return !(tileMod > 1 && ((py / 4) * tilesX + px / 4) % tileMod != tileRem);
-}
-__global__ __launch_bounds__(64) void synth_beam_flag_kernel(SceneView sc, int iteration, int tileMod, int tileRem,
-                                                             uint32_t npix, uint32_t *flag) {
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npix) return;
-  int px, py;
-  uint32_t f = 0;
-  if (ownedPixel(sc, p, tileMod, tileRem, px, py)) {
-    // the number of sets (medium edges of the base path: 0, 1, or 2 behind a mirror)
-    gvpm_camera_ray sets[2][5];
-    float w[2];
-    f = (uint32_t)cameraBeamSets(sc, iteration, px, py, sets, w);
-  }
-  flag[p] = f;
-}
-__global__ __launch_bounds__(64) void synth_beam_write_kernel(SceneView sc, int iteration, uint32_t npix,
-                                                              const uint32_t *flag, const uint32_t *offs,
-                                                              gvpm_camera_ray *out) {
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npix || !flag[p]) return;
-  const int px = (int)(p % (uint32_t)sc.width), py = (int)(p / (uint32_t)sc.width);
-  gvpm_camera_ray sets[2][5];
-  float w[2];
-  const int n = cameraBeamSets(sc, iteration, px, py, sets, w);
-  gvpm_camera_ray *dst = out + (size_t)offs[p] * 5;
-  for (int q = 0; q < n; ++q)
-    for (int k = 0; k < 5; ++k) dst[5 * q + k] = sets[q][k];
-}
 
 }  // namespace
 }  // namespace gvpm
+
+#include "synth_camera_kernels.inc"
 
 using namespace gvpm;
 
@@ -247,6 +121,8 @@ struct gvpm_devgen {
   SceneView view;
   Buf<SynthTri> tris;
   Buf<SynthMat> mats;
+  Buf<float> slices;    // the rough plastics' transmittance slices, GVPM_RTRANS_KNOTS floats each: what the device SynthMats' rtrans point at
+  bool glossy = false;  // a material above MAT_MIRROR: the glossy unit's kernels (synth_device_glossy.hip)
   Buf<uint32_t> counts, counted, nonEmpty, offs, countedOffs, neOffs, ctl;
   Buf<float> park;  // parked records of a batch's paths (synth_walk_kernel)
   // Outputs are BORROWED by the gather context (gvpm_upload_*_dev), whose kernels of up to three consecutive steps are
@@ -272,18 +148,77 @@ struct gvpm_devgen {
 
 extern "C" {
 
-int gvpm_devgen_create(const gvpm_devgen_scene *sc, int device, gvpm_devgen **out) {
-  if (!sc || !out) return GVPM_ERR_INVALID_ARG;
-  if (sc->n_tris && (!sc->tris || !sc->tri_mat)) return GVPM_ERR_INVALID_ARG;
-  if (sc->n_mats && (!sc->mat_kind || !sc->mat_albedo)) return GVPM_ERR_INVALID_ARG;
-  if (sc->max_depth + 1 > GVPM_SYNTH_MAXV || sc->width <= 0 || sc->height <= 0) return GVPM_ERR_INVALID_ARG;
-  if (hipSetDevice(device) != hipSuccess) return GVPM_ERR_NO_DEVICE;
+// ---- create: everything is validated on the host before the device is touched ----
+static thread_local const char *devgenError = "";
+static int refuse(int rc, const char *msg) {
+  devgenError = msg;
+  return rc;
+}
+const char *gvpm_devgen_last_error(void) { return devgenError; }
+
+// the scene's own rules (both entry points)
+static int checkScene(const gvpm_devgen_scene *sc, gvpm_devgen **out) {
+  if (!sc || !out) return refuse(GVPM_ERR_INVALID_ARG, "null scene or output pointer");
+  if (sc->n_tris && (!sc->tris || !sc->tri_mat)) return refuse(GVPM_ERR_INVALID_ARG, "null triangle arrays");
+  if (sc->n_mats && (!sc->mat_kind || !sc->mat_albedo)) return refuse(GVPM_ERR_INVALID_ARG, "null material arrays");
+  if (sc->max_depth + 1 > GVPM_SYNTH_MAXV || sc->width <= 0 || sc->height <= 0)
+    return refuse(GVPM_ERR_INVALID_ARG, "max_depth beyond the walk's vertex limit, or an empty frame");
+  for (uint32_t i = 0; i < sc->n_tris; ++i)
+    if (sc->tri_mat[i] < 0 || (uint32_t)sc->tri_mat[i] >= sc->n_mats) return refuse(GVPM_ERR_INVALID_ARG, "a triangle's material index is out of range");
+  return GVPM_OK;
+}
+
+// One material of gvpm_devgen_create_ex (include/gvpm_hip.h): the rules, in the order they are reported -- what the table of
+// gvpm_upload_bsdfs asks of the same kinds (bsdf_table.h), in its words.
+static int checkMaterial(const gvpm_devgen_scene *sc, const gvpm_devgen_material *mats, uint32_t i) {
+  const int kind = sc->mat_kind[i];
+  const gvpm_devgen_material &m = mats[i];
+  if (kind < MAT_LAMBERT || kind > MAT_MIXTURE) return refuse(GVPM_ERR_INVALID_ARG, "material kind outside the generators' set (0 .. 11)");
+  if (m.reserved[0] | m.reserved[1] | m.reserved[2]) return refuse(GVPM_ERR_INVALID_ARG, "material: the reserved words are zero");
+  if (kind == MAT_ROUGHPLASTIC) {
+    if (!m.rtrans) return refuse(GVPM_ERR_INVALID_ARG, "rough plastic: the transmittance slice is missing");
+    for (int j = 0; j < GVPM_RTRANS_KNOTS; ++j)
+      if (!(m.rtrans[j] >= 0.f && m.rtrans[j] <= 1.f)) return refuse(GVPM_ERR_INVALID_ARG, "rough plastic: slice values are finite and in [0, 1]");
+  }
+  if (kind == MAT_WARD_ANISO || kind == MAT_ROUGHCONDUCTOR_ANISO) {
+    const double sl = std::sqrt(m.tangent[0] * m.tangent[0] + m.tangent[1] * m.tangent[1] + m.tangent[2] * m.tangent[2]);
+    if (!(std::fabs(sl - 1.0) <= 1e-3)) return refuse(GVPM_ERR_INVALID_ARG, "anisotropic Ward / rough conductor: the tangent is a unit vector (to 1e-3)");
+    if (!bsdfAlphaValid((float)m.exponent) || !bsdfAlphaValid((float)m.alpha_v))
+      return refuse(GVPM_ERR_INVALID_ARG, "anisotropic Ward / rough conductor: alphaU, alphaV >= 1e-4");
+  }
+  if (kind == MAT_WARD || kind == MAT_WARD_ANISO) {
+    if (m.distribution < GVPM_WARD_WARD || m.distribution > GVPM_WARD_BALANCED) return refuse(GVPM_ERR_UNSUPPORTED, "Ward: variant ward / ward-duer / balanced");
+  } else if (kind == MAT_ROUGHCONDUCTOR || kind == MAT_ROUGHCONDUCTOR_ANISO || kind == MAT_ROUGHPLASTIC || kind == MAT_ROUGHDIELECTRIC) {
+    if (m.distribution != GVPM_MICROFACET_BECKMANN && m.distribution != GVPM_MICROFACET_GGX && m.distribution != GVPM_MICROFACET_PHONG)
+      return refuse(GVPM_ERR_UNSUPPORTED, kind == MAT_ROUGHPLASTIC      ? "rough plastic: Beckmann, GGX or Phong"
+                                          : kind == MAT_ROUGHDIELECTRIC ? "rough dielectric: Beckmann, GGX or Phong"
+                                                                        : "rough conductor: Beckmann, GGX or Phong / Ashikhmin-Shirley");
+  }
+  if (m.bsdf < -1) return refuse(GVPM_ERR_INVALID_ARG, "material: bsdf is -1 (no table entry) or the index of the material's first head");
+  if (kind == MAT_MIXTURE) {
+    // (sampleMixture divides by w_0 + w_1: the table's rule for the weights)
+    if (!(m.mix_w[0] >= 0.0 && m.mix_w[0] <= FLT_MAX) || !(m.mix_w[1] >= 0.0 && m.mix_w[1] <= FLT_MAX) || !(m.mix_w[0] + m.mix_w[1] > 0.0))
+      return refuse(GVPM_ERR_INVALID_ARG, "mixture: weights finite and >= 0, their sum > 0");
+    for (int c = 0; c < 2; ++c)
+      if (m.child[c] < 0 || (uint32_t)m.child[c] >= sc->n_mats) return refuse(GVPM_ERR_INVALID_ARG, "mixture: a child is the index of a material of the scene");
+    for (int c = 0; c < 2; ++c) {
+      const int ck = sc->mat_kind[m.child[c]];
+      if (ck != MAT_LAMBERT && ck != MAT_ROUGHCONDUCTOR && ck != MAT_ROUGHCONDUCTOR_ANISO)
+        return refuse(GVPM_ERR_UNSUPPORTED, "mixture: a child is the Lambertian or a rough conductor (one component each; no mixture as a child)");
+    }
+  }
+  return GVPM_OK;
+}
+
+// `dm`: the materials beyond kind and albedo (null: the closed set, every kind above MAT_MIRROR has been refused)
+static int createCommon(const gvpm_devgen_scene *sc, const gvpm_devgen_material *dm, int device, gvpm_devgen **out) {
+  if (hipSetDevice(device) != hipSuccess) return refuse(GVPM_ERR_NO_DEVICE, "no such HIP device");
   gvpm_devgen *g = new (std::nothrow) gvpm_devgen();
-  if (!g) return GVPM_ERR_HIP;
+  if (!g) return refuse(GVPM_ERR_HIP, "out of host memory");
   g->device = device;
   auto bail = [&](int rc) {
     gvpm_devgen_destroy(g);
-    return rc;
+    return refuse(rc, "a HIP call failed while the generator was set up");
   };
   if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) return bail(GVPM_ERR_HIP);
   std::vector<SynthTri> tris(sc->n_tris);
@@ -294,8 +229,9 @@ int gvpm_devgen_create(const gvpm_devgen_scene *sc, int device, gvpm_devgen **ou
     tris[i].e2 = V3(t[6], t[7], t[8]);
     tris[i].n = V3(t[9], t[10], t[11]);
     tris[i].mat = sc->tri_mat[i];
-    if (tris[i].mat < 0 || (uint32_t)tris[i].mat >= sc->n_mats) return bail(GVPM_ERR_INVALID_ARG);
   }
+  // the rough plastics' slices, one after the other in device memory the generator owns
+  std::vector<float> slices;
   std::vector<SynthMat> mats(sc->n_mats);
   for (uint32_t i = 0; i < sc->n_mats; ++i) {
     mats[i].kind = sc->mat_kind[i];
@@ -303,9 +239,38 @@ int gvpm_devgen_create(const gvpm_devgen_scene *sc, int device, gvpm_devgen **ou
     mats[i].spec = V3(0.0);
     mats[i].exponent = mats[i].specWeight = 0.0;
     mats[i].bsdf = -1;
-    // (the device generators' closed set: Lambertian, index-matched boundary, mirror -- a Phong wall's parameters do not
-    // travel in gvpm_devgen_scene: such scenes are shot on the host)
-    if (mats[i].kind < 0 || mats[i].kind > MAT_MIRROR) return bail(GVPM_ERR_UNSUPPORTED);
+    if (!dm) continue;
+    const gvpm_devgen_material &m = dm[i];
+    SynthMat &o = mats[i];
+    o.spec = V3(m.spec[0], m.spec[1], m.spec[2]);
+    o.exponent = m.exponent;
+    o.specWeight = m.spec_weight;
+    o.bsdf = m.bsdf;
+    o.eta = V3(m.eta[0], m.eta[1], m.eta[2]);
+    o.k = V3(m.k[0], m.k[1], m.k[2]);
+    o.distribution = m.distribution;
+    o.coatEta = m.coat_eta;
+    o.fdr = m.fdr;
+    o.nonlinear = m.nonlinear;
+    o.alphaV = m.alpha_v;
+    o.tangent = V3(m.tangent[0], m.tangent[1], m.tangent[2]);
+    for (int c = 0; c < 2; ++c) {
+      o.child[c] = m.child[c];
+      o.mixW[c] = m.mix_w[c];
+    }
+    if (o.kind == MAT_ROUGHPLASTIC) slices.insert(slices.end(), m.rtrans, m.rtrans + GVPM_RTRANS_KNOTS);
+    if (o.kind > MAT_MIRROR) g->glossy = true;
+  }
+  if (!slices.empty()) {
+    if (g->slices.ensure(slices.size()) != hipSuccess ||
+        hipMemcpy(g->slices.p, slices.data(), slices.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+      return bail(GVPM_ERR_HIP);
+    size_t at = 0;
+    for (auto &o : mats)
+      if (o.kind == MAT_ROUGHPLASTIC) {
+        o.rtrans = g->slices.p + at;  // (a device address: the host never reads through it)
+        at += GVPM_RTRANS_KNOTS;
+      }
   }
   if (g->tris.ensure(tris.size() + 1) != hipSuccess || g->mats.ensure(mats.size() + 1) != hipSuccess) return bail(GVPM_ERR_HIP);
   if (!tris.empty() && hipMemcpy(g->tris.p, tris.data(), tris.size() * sizeof(SynthTri), hipMemcpyHostToDevice) != hipSuccess)
@@ -344,14 +309,37 @@ int gvpm_devgen_create(const gvpm_devgen_scene *sc, int device, gvpm_devgen **ou
   v.minDepth = sc->min_depth;
   v.cameraSphere = sc->camera_sphere;
   *out = g;
+  devgenError = "";
   return GVPM_OK;
+}
+
+int gvpm_devgen_create(const gvpm_devgen_scene *sc, int device, gvpm_devgen **out) {
+  if (int rc = checkScene(sc, out)) return rc;
+  // (the closed set: Lambertian, index-matched boundary, mirror -- a glossy wall's parameters do not travel in gvpm_devgen_scene:
+  // gvpm_devgen_create_ex takes them)
+  auto bail = [](int rc) {
+    return refuse(rc, "material kind outside gvpm_devgen_create's closed set (Lambertian, index-matched, mirror): gvpm_devgen_create_ex");
+  };
+  for (uint32_t i = 0; i < sc->n_mats; ++i) {
+    const int kind = sc->mat_kind[i];
+    if (kind < 0 || kind > MAT_MIRROR) return bail(GVPM_ERR_UNSUPPORTED);
+  }
+  return createCommon(sc, nullptr, device, out);
+}
+
+int gvpm_devgen_create_ex(const gvpm_devgen_scene *sc, const gvpm_devgen_material *mats, uint32_t n_mats, int device, gvpm_devgen **out) {
+  if (int rc = checkScene(sc, out)) return rc;
+  if (n_mats != sc->n_mats || (n_mats && !mats)) return refuse(GVPM_ERR_INVALID_ARG, "one gvpm_devgen_material per material of the scene");
+  for (uint32_t i = 0; i < n_mats; ++i)
+    if (int rc = checkMaterial(sc, mats, i)) return rc;
+  return createCommon(sc, mats, device, out);
 }
 
 int gvpm_devgen_destroy(gvpm_devgen *g) {
   if (!g) return GVPM_ERR_INVALID_ARG;
   (void)hipSetDevice(g->device);
   if (g->stream) (void)hipStreamSynchronize(g->stream);
-  g->tris.release(); g->mats.release();
+  g->tris.release(); g->mats.release(); g->slices.release();
   g->counts.release(); g->counted.release(); g->nonEmpty.release(); g->offs.release(); g->countedOffs.release();
   g->neOffs.release(); g->ctl.release(); g->park.release();
   for (auto &o : g->pout) {
@@ -403,8 +391,8 @@ static int shootCommon(gvpm_devgen *g, int iteration, uint64_t capacity, int bea
     // one round of waves (two per SIMD at this kernel's registers), each walking its share of the batch with refill
     const uint32_t chunk = std::max(64u, (((m + 2047u) / 2048u) + 63u) & ~63u);  // (1024 / 4096 / 8192 shares: the same)
     const unsigned nb = (m + chunk - 1) / chunk;
-    hipLaunchKernelGGL(synth_walk_kernel, dim3(nb), dim3(64), 0, s, g->view, iteration, base, m, chunk, beams, g->park.p, stride,
-                       g->counts.p, g->counted.p, g->nonEmpty.p);
+    (g->glossy ? synthLaunchWalk_glossy : synthLaunchWalk)(s, nb, g->view, iteration, base, m, chunk, beams, g->park.p, stride, g->counts.p,
+                                                           g->counted.p, g->nonEmpty.p);
     SY_TRY(exclusiveSumU32(g->scanTmp, g->counts.p, g->offs.p, m, s));
     SY_TRY(exclusiveSumU32(g->scanTmp, g->counted.p, g->countedOffs.p, m, s));
     SY_TRY(exclusiveSumU32(g->scanTmp, g->nonEmpty.p, g->neOffs.p, m, s));
@@ -466,16 +454,15 @@ int gvpm_devgen_camera_beams(gvpm_devgen *g, int iteration, int tile_mod, int ti
   SY_TRY(g->pixOffs.ensure((size_t)npix + 1));
   const unsigned nb = (npix + 63) / 64;
   SY_TRY(hipMemsetAsync(g->pixFlag.p + npix, 0, 4, s));
-  hipLaunchKernelGGL(synth_beam_flag_kernel, dim3(nb), dim3(64), 0, s, g->view, iteration, tile_mod, tile_rem, npix,
-                     g->pixFlag.p);
+  (g->glossy ? synthLaunchBeamFlag_glossy : synthLaunchBeamFlag)(s, nb, g->view, iteration, tile_mod, tile_rem, npix, g->pixFlag.p);
   SY_TRY(exclusiveSumU32(g->scanTmp, g->pixFlag.p, g->pixOffs.p, npix + 1, s));
   uint32_t total = 0;
   SY_TRY(hipMemcpyAsync(&total, g->pixOffs.p + npix, 4, hipMemcpyDeviceToHost, s));
   SY_TRY(hipStreamSynchronize(s));
   g->raysIdx = (g->raysIdx + 1) % 3;
   SY_TRY(g->raysOut[g->raysIdx].ensure((size_t)total * 5 + 5));
-  hipLaunchKernelGGL(synth_beam_write_kernel, dim3(nb), dim3(64), 0, s, g->view, iteration, npix, g->pixFlag.p, g->pixOffs.p,
-                     g->raysOut[g->raysIdx].p);
+  (g->glossy ? synthLaunchBeamWrite_glossy : synthLaunchBeamWrite)(s, nb, g->view, iteration, npix, g->pixFlag.p, g->pixOffs.p,
+                                                                   g->raysOut[g->raysIdx].p);
   SY_TRY(hipStreamSynchronize(s));
   SY_TRY(hipGetLastError());
   *rays_dev = g->raysOut[g->raysIdx].p;

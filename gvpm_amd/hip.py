@@ -24,6 +24,7 @@ SYMBOLS = [
     "gvpm_set_global_scale", "gvpm_get_stats", "gvpm_get_exact_shift_count", "gvpm_get_kernel_time", "gvpm_get_phase_time", "gvpm_download_accum",
     "gvpm_download_accum_dev", "gvpm_download_film", "gvpm_synchronize", "gvpm_comm_unique_id", "gvpm_comm_init",
     "gvpm_allreduce_accum", "gvpm_allreduce_film", "gvpm_download_film_dev", "gvpm_devgen_create",
+    "gvpm_devgen_create_ex", "gvpm_devgen_last_error",
     "gvpm_devgen_destroy", "gvpm_devgen_shoot_photons", "gvpm_devgen_shoot_beams", "gvpm_devgen_camera_beams", "gvpm_devgen_read",
     "gvpm_poisson_preset", "gvpm_poisson_solve", "gvpm_poisson_solve_dev",
     "gvpm_host_alloc", "gvpm_host_alloc_photons", "gvpm_host_free", "gvpm_prefetch_photons", "gvpm_prefetch_camera_beams",
@@ -100,6 +101,9 @@ def lib():
         L.gvpm_allreduce_accum.argtypes = [vp]
         L.gvpm_allreduce_film.argtypes = [vp, vp]
         L.gvpm_devgen_create.argtypes = [C.POINTER(abi.DevgenScene), C.c_int, C.POINTER(vp)]
+        L.gvpm_devgen_create_ex.argtypes = [C.POINTER(abi.DevgenScene), vp, C.c_uint32, C.c_int, C.POINTER(vp)]
+        L.gvpm_devgen_last_error.argtypes = []
+        L.gvpm_devgen_last_error.restype = C.c_char_p
         L.gvpm_devgen_destroy.argtypes = [vp]
         L.gvpm_devgen_shoot_photons.argtypes = [vp, C.c_int, C.c_uint64, C.POINTER(abi.PhotonSoA), C.POINTER(C.c_uint64)]
         L.gvpm_devgen_shoot_beams.argtypes = [vp, C.c_int, C.c_uint64, C.POINTER(abi.PhotonSoA), C.POINTER(vp),
@@ -865,14 +869,21 @@ class DeviceGenerator:
     Outputs are device pointers owned by the generator; it rotates three output buffers per kind, so an output stays
     untouched for the two following calls of the same kind (the kernels of up to three steps are in flight)."""
 
-    def __init__(self, synth_scene, device=0):
+    def __init__(self, synth_scene, device=0, glossy=False):
+        """glossy=False: gvpm_devgen_create, the closed set Lambertian / index-matched / mirror (any other material is refused).
+        glossy=True: gvpm_devgen_create_ex with the scene's devgen_materials(): every material the host generators walk."""
         self._scene = synth_scene  # keeps the host arrays alive during create
         self._h = C.c_void_p()
         d = synth_scene.devgen_scene()
-        rc = lib().gvpm_devgen_create(C.byref(d), device, C.byref(self._h))
+        if glossy:
+            mats = synth_scene.devgen_materials()
+            rc = lib().gvpm_devgen_create_ex(C.byref(d), mats, len(mats), device, C.byref(self._h))
+        else:
+            rc = lib().gvpm_devgen_create(C.byref(d), device, C.byref(self._h))
         if rc != 0:
             self._h = None
-            raise GvpmError(rc, "gvpm_devgen_create failed")  # (status kept: GVPM_ERR_NO_DEVICE / _HIP / _INVALID_ARG)
+            # (status kept: GVPM_ERR_NO_DEVICE / _HIP / _INVALID_ARG / _UNSUPPORTED)
+            raise GvpmError(rc, f"gvpm_devgen_create{'_ex' if glossy else ''} failed: {lib().gvpm_devgen_last_error().decode()}")
 
     def close(self):
         if getattr(self, "_h", None):

@@ -23,6 +23,8 @@ def lib():
         L.gvpm_synth_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_uint32]
         L.gvpm_synth_destroy.argtypes = [C.c_void_p]
         L.gvpm_synth_devgen_scene.argtypes = [C.c_void_p, C.POINTER(abi.DevgenScene)]
+        L.gvpm_synth_set_min_depth.argtypes = [C.c_void_p, C.c_int]
+        L.gvpm_synth_devgen_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.gvpm_synth_params.argtypes = [C.c_void_p, C.POINTER(abi.Params)]
         L.gvpm_synth_medium.argtypes = [C.c_void_p, C.POINTER(abi.Medium)]
         L.gvpm_synth_triangles.argtypes = [C.c_void_p, C.POINTER(abi.Triangles)]
@@ -218,6 +220,24 @@ class SynthScene:
         if rc != 0:
             raise RuntimeError(f"gvpm_synth_devgen_scene failed: {rc}")
         return d
+
+    def set_min_depth(self, min_depth):
+        """GPMConfig minDepth of the light-path walk (host generators, params() and devgen_scene() carry it): at 2 no photon or beam
+        is reconnected from the emitter"""
+        if lib().gvpm_synth_set_min_depth(self._h, min_depth) != 0:
+            raise ValueError(f"set_min_depth({min_depth}): outside [0, maxDepth)")
+
+    def devgen_materials(self):
+        """The scene's materials beyond kind and albedo, as gvpm_devgen_create_ex takes them: a ctypes array of
+        abi.DevgenMaterial, one per material (slice pointers owned by this object: keep it alive)."""
+        n = self.devgen_scene().n_mats
+        out = (abi.DevgenMaterial * n)()
+        rc = lib().gvpm_synth_devgen_materials(self._h, out, n)
+        if rc == abi.GVPM_ERR_STATE:
+            raise RuntimeError("a rough-plastic material has no transmittance slice: set_rtrans first")
+        if rc != 0:
+            raise RuntimeError(f"gvpm_synth_devgen_materials failed: {rc}")
+        return out
 
     def shoot_photons(self, iteration, capacity):
         """-> (abi.Photons, nb_paths)"""

@@ -75,6 +75,41 @@ int gvpm_synth_devgen_scene(gvpm_synth *s, gvpm_devgen_scene *out) {
   return GVPM_OK;
 }
 
+int gvpm_synth_set_min_depth(gvpm_synth *s, int min_depth) {
+  if (!s || min_depth < 0 || min_depth >= s->scene.maxDepth) return GVPM_ERR_INVALID_ARG;
+  s->scene.minDepth = min_depth;
+  return GVPM_OK;
+}
+
+int gvpm_synth_devgen_materials(const gvpm_synth *s, gvpm_devgen_material *out, uint32_t n) {
+  if (!s || !out || n != (uint32_t)s->scene.mats.size()) return GVPM_ERR_INVALID_ARG;
+  if (!s->scene.rtransComplete()) return GVPM_ERR_STATE;  // (as the shoot calls: a rough plastic without its slice)
+  memset(out, 0, n * sizeof(*out));
+  auto put = [](double *d, gvpm::V3 v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
+  for (uint32_t i = 0; i < n; ++i) {
+    const gvpm::SynthMat &m = s->scene.mats[i];
+    gvpm_devgen_material &o = out[i];
+    put(o.spec, m.spec);
+    o.exponent = m.exponent;
+    o.spec_weight = m.specWeight;
+    put(o.eta, m.eta);
+    put(o.k, m.k);
+    o.coat_eta = m.coatEta;
+    o.fdr = m.fdr;
+    o.alpha_v = m.alphaV;
+    put(o.tangent, m.tangent);
+    o.rtrans = m.kind == gvpm::MAT_ROUGHPLASTIC ? m.rtrans : nullptr;
+    o.bsdf = m.bsdf;
+    o.distribution = m.distribution;
+    o.nonlinear = m.nonlinear;
+    for (int c = 0; c < 2; ++c) {
+      o.mix_w[c] = m.mixW[c];
+      o.child[c] = m.child[c];
+    }
+  }
+  return GVPM_OK;
+}
+
 int gvpm_synth_params(const gvpm_synth *s, gvpm_params *out) {
   if (!s || !out) return GVPM_ERR_INVALID_ARG;
   gvpm::defaultParams(s->scene, *out);

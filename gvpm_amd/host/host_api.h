@@ -12,6 +12,15 @@ gvpm_synth *gvpm_synth_create(const char *scene, int width, int height, uint32_t
 void gvpm_synth_destroy(gvpm_synth *s);
 /* the scene as the device-side generators take it (gvpm_devgen_create, include/gvpm_hip.h); the arrays stay owned by `s` */
 int gvpm_synth_devgen_scene(gvpm_synth *s, gvpm_devgen_scene *out);
+/* GPMConfig minDepth of the light-path walk (0 at create): the photon flattening stores path vertices from index max(minDepth + 1, 2),
+ * the beam flattening edges from index max(minDepth, 1) (GPhotonMap::tryAppend, LTBeamMap::tryAppendLT) -- at 2 no record is reconnected
+ * from the emitter.  Host generators, gvpm_synth_params and gvpm_synth_devgen_scene all carry it.  GVPM_ERR_INVALID_ARG outside
+ * [0, maxDepth). */
+int gvpm_synth_set_min_depth(gvpm_synth *s, int min_depth);
+/* the scene's materials beyond kind and albedo, as gvpm_devgen_create_ex takes them: `n` = the scene's material count (n_mats of
+ * gvpm_synth_devgen_scene; GVPM_ERR_INVALID_ARG otherwise); a slice pointer stays owned by `s`.  GVPM_ERR_STATE, and nothing written,
+ * when a rough-plastic material has no transmittance slice yet (gvpm_synth_set_rtrans) -- where the shoot calls fail too */
+int gvpm_synth_devgen_materials(const gvpm_synth *s, gvpm_devgen_material *out, uint32_t n);
 int gvpm_synth_params(const gvpm_synth *s, gvpm_params *out);
 int gvpm_synth_medium(const gvpm_synth *s, gvpm_medium *out);
 int gvpm_synth_triangles(gvpm_synth *s, gvpm_triangles *out);

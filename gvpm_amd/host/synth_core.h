@@ -43,10 +43,13 @@ namespace gvpm {
 // the weights after the constructor's rescale; `albedo` = the Lambertian child's reflectance (what the records carry as parent_scat),
 // `exponent` = the smaller of the children's roughnesses: below 0.05 sampleNext picks ONE child per bounce and the material has a
 // table entry per child (bsdf, bsdf + 1), else one.  Its conductor children have entries of their own, which the mixture's name.
-// The glossy kinds are sampled by the HOST generators only: the device generator's closed set is Lambertian / index-matched /
-// mirror (gvpm_devgen_create refuses the others), and their fp64 pow / atan / log chains cost the device walk a third of its
-// time in registers alone when they were merely compiled in.
-#ifdef __HIP_DEVICE_COMPILE__
+// The glossy kinds cost the device walk a third of its time in registers alone when their fp64 pow / atan / log chains were merely
+// compiled in.  So the device pass compiles the GVPM_SYNTH_GLOSSY regions only for a unit that asks for them (GVPM_SYNTH_DEVICE_GLOSSY
+// defined before this header: csrc/synth_device_glossy.hip, kernels of its own); csrc/synth_device.hip's kernels stay the closed set
+// Lambertian / index-matched / mirror (gvpm_devgen_create refuses the others, gvpm_devgen_create_ex launches the glossy unit's kernels
+// for them).  The library is built without relocatable device code: each unit is a code object of its own, and the two device
+// instantiations of the functions below never meet.  The host pass of every unit sees the regions.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(GVPM_SYNTH_DEVICE_GLOSSY)
 #define GVPM_SYNTH_GLOSSY 0
 #else
 #define GVPM_SYNTH_GLOSSY 1
@@ -343,7 +346,7 @@ GVPM_HD inline double hgEval(double g, double cosWiWo) {
 // sample.y).  Isotropic: phi = 2 pi b and the exponent eU; else the azimuth of the first quadrant (sampleFirstQuadrant, :707-715)
 // mirrored into b's quadrant, with the exponent interpolated at it.  cos(theta_m) = a^(1 / (e + 2)), pdf = sqrt((eU + 2)(eV + 2))
 // / (2 pi) cos^(e + 1); the caller applies the `pdf < 1e-20` cut.
-inline void samplePhongDist(double au, double av, double a, double b, double &cosThetaM, double &phiM, double &pdfM) {
+GVPM_HD inline void samplePhongDist(double au, double av, double a, double b, double &cosThetaM, double &phiM, double &pdfM) {
   const double eU = phongDistExponent(au), eV = phongDistExponent(av);
   double ex = eU;
   if (au == av) {
@@ -367,7 +370,7 @@ inline void samplePhongDist(double au, double av, double a, double b, double &co
 // One bounce off an isotropic rough conductor: RoughConductor::sample, sampleVisible = false (roughconductor.cpp:321-389 with
 // MicrofacetDistribution::sampleAll, microfacet.h:287-375): half vector m ~ D cos, wo = reflect(wi, m), weight = F D G (wi . m) /
 // (pdf_m cos_i), pdf = pdf_m / (4 |wo . m|).  (a, b) = (sample.x, sample.y).  False: the sample is lost.
-inline bool sampleConductor(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
+GVPM_HD inline bool sampleConductor(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
   const double alpha = pm.exponent, alphaSqr = alpha * alpha, cosWi = dot(n, wi);
   double tanThetaMSqr, pdfM, cosThetaM, phi = 2.0 * kPi * b;
   if (pm.distribution == GVPM_MICROFACET_PHONG) {
@@ -405,7 +408,7 @@ inline bool sampleConductor(const SynthMat &pm, V3 n, V3 wi, double a, double b,
 // sample.y).  Ward::sample with bRec.component = -1 (ward.cpp:268-327; roughness 0.5 (alphaU + alphaV) >= 0.05): phiH / thetaH
 // as written at :289-306; RoughConductor::sample without visible normals over MicrofacetDistribution::sampleAll's anisotropic
 // branch (microfacet.h:287-347).  False: the sample is lost.
-inline bool sampleAniso(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
+GVPM_HD inline bool sampleAniso(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
   V3 sp = pm.tangent - n * dot(n, pm.tangent);
   if (dot(sp, sp) < 1e-12) return false;
   sp = normalize(sp);
@@ -517,7 +520,7 @@ GVPM_HD inline double dielectricFresnelExt(double cI_, double &cT_, double eta) 
 // MicrofacetDistribution::sampleAll at the alpha Walter's trick scaled, 1.2 - 0.2 sqrt(|cos_i|) (:537-544); weight =
 // |D G wi.m / (pdf_m cos_i)| times the reflectance or the transmittance (EImportance: no compression factor), D and G at the
 // surface's own alpha; pdf = D'(m) cos_m (F | 1 - F) |dwh_dwo| (include/gvpm_hip.h).  False: the sample is lost.
-inline bool sampleDielectric(const SynthMat &pm, V3 n, V3 wi, double a, double b, double c, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
+GVPM_HD inline bool sampleDielectric(const SynthMat &pm, V3 n, V3 wi, double a, double b, double c, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
   const double cosN = dot(n, wi);
   if (cosN == 0) return false;
   const V3 nI = cosN > 0 ? n : -n;
@@ -571,7 +574,7 @@ inline bool sampleDielectric(const SynthMat &pm, V3 n, V3 wi, double a, double b
 // One bounce off a plastic surface as PathVertex::sampleNext does it (vertex.cpp:160-173): component selection, BSDF::sample
 // with bRec.component, then weight /= pdfComponent, pdf *= pdfComponent.  (a, b): the vertex's two random numbers (sample.x,
 // sample.y).  False: the sample is lost (the walk ends).  solidAngle = false: a Dirac bounce, pdf in the discrete measure.
-inline bool samplePlastic(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp,
+GVPM_HD inline bool samplePlastic(const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp,
                           int &compSel, bool &solidAngle) {
   if (pm.kind == MAT_ROUGHPLASTIC) {
     // PathVertex::sampleNext (vertex.cpp:160-173) over RoughPlastic (roughplastic.cpp): below alpha 0.05 sampleComponent
@@ -685,14 +688,14 @@ inline bool samplePlastic(const SynthMat &pm, V3 n, V3 wi, double a, double b, V
 
 // ---- the two-component mixture (src/bsdfs/mixturebsdf.cpp) ----
 // getRoughness of a child (diffuse.cpp:167-169, roughconductor.cpp:437-440)
-inline double mixtureChildRoughness(const SynthMat &cm) {
+GVPM_HD inline double mixtureChildRoughness(const SynthMat &cm) {
   if (cm.kind == MAT_ROUGHCONDUCTOR) return cm.exponent;
   if (cm.kind == MAT_ROUGHCONDUCTOR_ANISO) return 0.5 * (cm.exponent + cm.alphaV);
   return std::numeric_limits<double>::infinity();
 }
 // BSDF::eval (x cos) and BSDF::pdf of a child towards wo: the Lambertian (diffuse.cpp:110-127) or the rough conductor, either form,
 // without visible normals (roughconductor.cpp:257-319).  cos_i > 0 is the caller's.  False: an anisotropic child without a frame.
-inline bool mixtureChildEval(const SynthMat &cm, V3 n, V3 wi, V3 wo, V3 &f, double &pdf) {
+GVPM_HD inline bool mixtureChildEval(const SynthMat &cm, V3 n, V3 wi, V3 wo, V3 &f, double &pdf) {
   const double cosWi = dot(n, wi), cosWo = dot(n, wo);
   f = V3(0.0);
   pdf = 0.0;
@@ -725,7 +728,7 @@ inline bool mixtureChildEval(const SynthMat &cm, V3 n, V3 wi, V3 wo, V3 &f, doub
   return true;
 }
 // BSDF::sample(bRec, pdf, sample) of a child; `pdf` stays 0 where the child found no direction at all
-inline bool mixtureChildSample(const SynthMat &cm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
+GVPM_HD inline bool mixtureChildSample(const SynthMat &cm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf, uint32_t &comp) {
   pdf = 0.0;
   if (cm.kind == MAT_ROUGHCONDUCTOR) return sampleConductor(cm, n, wi, a, b, wo, weight, pdf, comp);
   if (cm.kind == MAT_ROUGHCONDUCTOR_ANISO) return sampleAniso(cm, n, wi, a, b, wo, weight, pdf, comp);
@@ -743,7 +746,7 @@ inline bool mixtureChildSample(const SynthMat &cm, V3 n, V3 wi, double a, double
 // divides by pdfComponent = p_c and multiplies the pdf by it.  Else component -1: sampleReuse(sample.x) picks the child that is
 // sampled, weight = (w_0 eval_0 + w_1 eval_1) / (p_0 pdf_0 + p_1 pdf_1) with the sampled child's eval = its weight times its pdf.
 // No random number beyond the vertex's two.  `mats`: the scene's materials (the children).  False: the sample is lost.
-inline bool sampleMixture(const SynthMat *mats, const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf,
+GVPM_HD inline bool sampleMixture(const SynthMat *mats, const SynthMat &pm, V3 n, V3 wi, double a, double b, V3 &wo, V3 &weight, double &pdf,
                           uint32_t &comp, int &compSel) {
   const double w[2] = {pm.mixW[0], pm.mixW[1]}, p[2] = {w[0] / (w[0] + w[1]), w[1] / (w[0] + w[1])};
   const SynthMat *ch[2] = {&mats[pm.child[0]], &mats[pm.child[1]]};
@@ -1311,6 +1314,11 @@ template <class RL, bool BEAMS> struct StreamPath {
     ++n;
     if (idx == 0) return;
     const StreamPath &path = *this;
+#if GVPM_SYNTH_GLOSSY
+    // (a plastic vertex is diffuse or not by the component it was SAMPLED through, which is known once its successor exists: vertex
+    // idx - 1 is classified here, before shiftCode reads lastDiffuse, and not when it was appended)
+    if (idx >= 2 && vertexIsDiffuse(sc, path[idx - 1])) lastDiffuse = (int)idx - 1;
+#endif
     // an interior vertex (it has a successor now) with a zero pdf rejects the whole path
     if (idx >= 2 && path[idx - 1].pdf == 0.0) bad = true;
     const V3 prefix = w;  // prod_{k < idx - 1}
@@ -1385,7 +1393,9 @@ template <class RL, bool BEAMS> struct StreamPath {
         recs.push_back(r);
       }
     }
-    if (vertexIsDiffuse(sc, path[idx])) lastDiffuse = (int)idx;
+#if !GVPM_SYNTH_GLOSSY
+    if (vertexIsDiffuse(sc, path[idx])) lastDiffuse = (int)idx;  // (the closed set: a vertex's class is known when it is appended)
+#endif
   }
   // after the walk: the whole-path rejection; returns what flattenBeams returns (photons: true)
   GVPM_HD bool finish() {

@@ -958,8 +958,9 @@ int gvpm_poisson_solve_dev(gvpm_context *h, const gvpm_poisson_params *params, i
 /* Photon shooting (GPMIntegrator's photon pass: gvpm_proc.cpp:125-209,278-350 with GPhotonMap::tryAppend /
  * LTBeamMap::tryAppendLT flattening) and camera-beam generation (randomWalkFromPixelToFirstDiffuse +
  * ShiftGatherPoint::generate, gvpm_gatherpoint.h:22-170, shift_cameraPath.h:29-133) on the GPU for scenes the
- * device can intersect itself: a triangle list, Lambertian / index-matched materials, one quad area light, one
- * homogeneous medium, a pinhole sensor.  The outputs are device-resident and go straight into
+ * device can intersect itself: a triangle list, the materials of the host generators (Lambertian / index-matched / mirror
+ * through gvpm_devgen_create, every glossy kind through gvpm_devgen_create_ex), one quad area light, one homogeneous medium, a
+ * pinhole sensor.  The outputs are device-resident and go straight into
  * gvpm_upload_photons_dev / gvpm_upload_beams_dev / gvpm_upload_camera_beams_dev: nothing crosses PCIe.
  * Same counter-based streams as the host generators of gvpm_amd/host (keyed by path / pixel index), so the
  * device reproduces the sequential host loop: same photon count, same path count, same order.              */
@@ -967,7 +968,7 @@ typedef struct gvpm_devgen_scene {
   uint32_t n_tris, n_mats;
   const double *tris;        /* 12 per triangle: v0, e1, e2, geometric normal   */
   const int32_t *tri_mat;    /* material index per triangle                      */
-  const int32_t *mat_kind;   /* 0 Lambertian, 1 index-matched medium boundary    */
+  const int32_t *mat_kind;   /* 0 Lambertian, 1 index-matched medium boundary, 2 mirror; 3..11 with gvpm_devgen_create_ex */
   const double *mat_albedo;  /* 3 per material                                   */
   double light_c[3], light_u[3], light_v[3], light_n[3], radiance[3], light_area;
   gvpm_medium medium;
@@ -981,7 +982,61 @@ typedef struct gvpm_devgen_scene {
                                 film, +y towards larger pixel rows: gvpm_sensor's to_world); ALL ZERO = identity (ABI 3) */
 } gvpm_devgen_scene;
 typedef struct gvpm_devgen gvpm_devgen;
+/* gvpm_devgen_create walks the closed set Lambertian (0) / index-matched boundary (1) / mirror (2) and refuses every other
+ * mat_kind with GVPM_ERR_UNSUPPORTED; scene and kinds are validated on the host before the device is touched.            */
 int gvpm_devgen_create(const gvpm_devgen_scene *scene, int device, gvpm_devgen **out);
+/* What a material carries beyond its kind and albedo (scene->mat_kind, scene->mat_albedo): the parameters of the glossy kinds, so that
+ * the device generators walk every material the host generators of gvpm_amd/host walk.  mat_kind may then be any kind of the host
+ * walk: 3 Phong, 4 rough conductor, 5 Ward, 6 rough plastic, 7 plastic, 8 anisotropic Ward, 9 anisotropic rough conductor, 10 rough
+ * dielectric, 11 two-child mixture.  Each sampler follows the reference lines quoted here (and, with the arithmetic, in
+ * gvpm_amd/host/synth_core.h); component selection is PathVertex::sampleNext's (vertex.cpp:160-180) for every kind.
+ *   spec         Phong (phong.cpp:188-247), Ward (ward.cpp:268-327), conductor (roughconductor.cpp:321-389), plastics (roughplastic.cpp:
+ *                439-501, plastic.cpp:451-466): the specular reflectance; rough dielectric (roughdielectric.cpp:513-617): the specular
+ *                reflectance
+ *   exponent     Phong: the exponent (one component per bounce where sqrt(2 / (2 + exponent)) < 0.05, phong.cpp:293-329); every
+ *                other kind: alpha, alphaU of the anisotropic kinds; mixture: the smaller of its children's roughnesses
+ *   spec_weight  m_specularSamplingWeight (phong.cpp:93-97, ward.cpp, roughplastic.cpp:532-564, plastic.cpp:451-466)
+ *   bsdf         index of the material's first head in the table of gvpm_upload_bsdfs (-1: none): what the records' parent_g name.
+ *                Phong / rough plastic / mixture below roughness 0.05: a head per component met; rough dielectric: bsdf = met
+ *                from the front, the next head = met from the back
+ *   eta, k       conductor: the complex index per channel (fresnelConductorExact, util.cpp:747-769); rough dielectric: k = the
+ *                specular transmittance
+ *   distribution the microfacet kinds: GVPM_MICROFACET_* (MicrofacetDistribution::sampleAll, microfacet.h:287-375, without
+ *                visible normals); Ward: GVPM_WARD_* (ward.cpp:230-266)
+ *   coat_eta     plastics: the coating's relative index; rough dielectric: m_eta, the index below the front over the index above
+ *   fdr          plastics: Fdr (rough: with its slice, roughplastic.cpp:439-501; smooth: m_fdrInt, plastic.cpp); nonlinear: m_nonlinear
+ *   rtrans       rough plastic: its transmittance slice, GVPM_RTRANS_KNOTS values in [0, 1] (RoughTransmittance::eval at fixed eta
+ *                and alpha, rtrans.h:183-236); read during the call and copied to device memory the generator owns; NULL for
+ *                every other kind
+ *   alpha_v, tangent   the anisotropic kinds: alphaV and the surface's unit tangent in world space, the direction alphaU belongs to
+ *                (ward.cpp:289-306, microfacet.h:287-347); the rules of the table's frame entry hold
+ *   child, mix_w the mixture (mixturebsdf.cpp:247-314): two materials of this scene out of Lambertian / rough conductor of either
+ *                form, and their weights after the constructor's rescale
+ *   reserved     zero
+ * gvpm_devgen_create_ex validates scene and materials on the host BEFORE the device is touched, so every refusal is reached on a
+ * machine without a GPU, where a well-formed scene returns GVPM_ERR_NO_DEVICE.  GVPM_ERR_INVALID_ARG: n_mats != scene->n_mats, an
+ * unknown kind, a non-zero reserved word, a rough plastic without its slice or with a slice value outside [0, 1] or not finite, an
+ * anisotropic kind whose tangent is not a unit vector to 1e-3 or whose alphaU / alphaV is below 1e-4, a mixture child index out of
+ * range, mixture weights that are negative, not finite or sum to zero, a `bsdf` below -1.  GVPM_ERR_UNSUPPORTED: a microfacet `distribution` that is not Beckmann, GGX or Phong, a Ward variant outside
+ * GVPM_WARD_*, a mixture child that is not Lambertian or a rough conductor of either form.  gvpm_devgen_last_error() names the
+ * refusal of the calling thread's last gvpm_devgen_create / _ex ("" after a success).
+ * A generator made here launches the closed-set kernels when no material is above kind 2 -- bit for bit gvpm_devgen_create's output --
+ * and the glossy unit's kernels otherwise.                                                                                          */
+typedef struct gvpm_devgen_material {
+  double spec[3];
+  double exponent, spec_weight;
+  double eta[3], k[3];
+  double coat_eta, fdr;
+  double alpha_v, tangent[3];
+  double mix_w[2];
+  const float *rtrans;
+  int32_t bsdf, distribution, nonlinear;
+  int32_t child[2];
+  int32_t reserved[3];
+} gvpm_devgen_material;
+int gvpm_devgen_create_ex(const gvpm_devgen_scene *scene, const gvpm_devgen_material *mats, uint32_t n_mats, int device,
+                          gvpm_devgen **out);
+const char *gvpm_devgen_last_error(void);
 int gvpm_devgen_destroy(gvpm_devgen *g);
 /* shoots light paths 0, 1, 2, ... of `iteration` until `capacity` photons are stored; *dev_soa receives device
  * pointers owned by the generator, *nb_paths the number of paths shot.  The generator rotates THREE output sets per
