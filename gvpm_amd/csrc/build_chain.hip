@@ -324,19 +324,27 @@ template <int B, int MODE> __global__ __launch_bounds__(64) __attribute__((amdgp
   // The two roles INTERLEAVED over the launch (workgroups are dispatched in index order): with the planner's blocks first,
   // they alone fill the chip -- a few thousand single-wave workgroups of 11 KB -- and the scatter starts when they end.
   const uint32_t b = blockIdx.x, pslot = b / t.every;
+  // (GVPM_TAIL_ONLY: a probe for scripts/regs.sh, never the library's build -- 1 compiles the scatter out, 2 the planner:
+  // which role owns the registers and the spills)
+#if !defined(GVPM_TAIL_ONLY) || GVPM_TAIL_ONLY == 1
   if (b % t.every == 0u && pslot < t.nPlan) {
     // (the 3D grid: 64 / B chunks side by side, tile_walk.h planBodyQ; bundle cells: one chunk at a time)
     if (a.grid.mode != 1 && t.planGroups)
       planBodyQ<B, TAIL_PLAN_STAGE>(a, t.ntiles, t.target, t.items, t.itemCount, t.itemOff, t.blockTotal, t.itemCap, pslot, t.nPlan,
                                     *reinterpret_cast<PlanLdsQ<B, TAIL_PLAN_STAGE> *>(ldsRaw));
     else
-      planBody<B, TAIL_PLAN_STAGE>(a, t.ntiles, t.target, t.items, t.itemCount, t.itemOff, t.blockTotal, t.itemCap, pslot, t.nPlan,
+      planBody<B, TAIL_PLAN_STAGE, true>(a, t.ntiles, t.target, t.items, t.itemCount, t.itemOff, t.blockTotal, t.itemCap, pslot, t.nPlan,
                                    *reinterpret_cast<PlanLds<B, TAIL_PLAN_STAGE> *>(ldsRaw));
   }
   else
+#endif
+#if !defined(GVPM_TAIL_ONLY) || GVPM_TAIL_ONLY == 2
     reorderBody<MODE>(t.raw, t.keys, t.rank, t.cellStart, t.n, a.cfg, a.bvh, a.tri4, a.ntri, t.dmax, t.ng, t.nearExt, t.extCap, t.hot,
                       t.cold, t.overflow, t.origIdx, t.sub, t.ncells, b - min(t.nPlan, (b + t.every - 1u) / t.every), t.counts,
                       t.subCount, *reinterpret_cast<ReorderLds *>(ldsRaw));
+#else
+    (void)0;
+#endif
   if (!lastBlockArrives(t.ctl, blockIdx.x, gridDim.x)) return;
   if (threadIdx.x == 0) {
     // what export_u32_kernel handed the host: pair blocks, overflowed near lists, extension cursor, items, bundle flag
@@ -363,15 +371,16 @@ template <int B, int MODE> __global__ __launch_bounds__(64) __attribute__((amdgp
 
 template <int B>
 static void launchTail(int mode, uint32_t grid, hipStream_t s, const GatherArgs &a, const TailArgs &t) {
-  if (mode == 0) hipLaunchKernelGGL((chain_tail_kernel<B, 0>), dim3(grid), dim3(64), 0, s, a, t);
-  else if (mode == 2) hipLaunchKernelGGL((chain_tail_kernel<B, 2>), dim3(grid), dim3(64), 0, s, a, t);
-  else hipLaunchKernelGGL((chain_tail_kernel<B, 1>), dim3(grid), dim3(64), 0, s, a, t);
+  if (mode == NEAR_SCAN_SCALAR) hipLaunchKernelGGL((chain_tail_kernel<B, NEAR_SCAN_SCALAR>), dim3(grid), dim3(64), 0, s, a, t);
+  else if (mode == NEAR_SCAN_VECTOR) hipLaunchKernelGGL((chain_tail_kernel<B, NEAR_SCAN_VECTOR>), dim3(grid), dim3(64), 0, s, a, t);
+  else if (mode == NEAR_GRID) hipLaunchKernelGGL((chain_tail_kernel<B, NEAR_GRID>), dim3(grid), dim3(64), 0, s, a, t);
+  else hipLaunchKernelGGL((chain_tail_kernel<B, NEAR_BVH>), dim3(grid), dim3(64), 0, s, a, t);
 }
 
 void launch_build_chain(ChainArgs c, const GatherArgs &a, const gvpm_photon_soa &raw, int beamsPerWave, uint32_t target, uint4 *items,
                         uint2 *itemOff, uint32_t itemCap, float dmax, const NearGrid &ng, uint32_t extCap, uint32_t *origIdx,
                         uint32_t *hostOut, bool initBuckets, hipStream_t s, uint32_t pairCapBlocks, uint32_t unitCap, uint32_t unitPairs,
-                        bool fullVis, bool planGroups) {
+                        bool fullVis, bool planGroups, bool nearScalar) {
   c.nPhBlocks = (c.n + 255u) / 256u;
   c.nBeamBlocks = (c.nsets + 255u) / 256u;
   if (initBuckets) hipLaunchKernelGGL(chain_init_buckets_kernel, dim3(1), dim3(768), 0, s, c.buckets);
@@ -427,7 +436,7 @@ void launch_build_chain(ChainArgs c, const GatherArgs &a, const gvpm_photon_soa 
   t.unitCap = unitCap;
   t.unitPairs = unitPairs ? unitPairs : 1u;
   t.fullVis = fullVis ? 1u : 0u;
-  const int mode = a.ntri <= 64u ? 0 : (ng.start ? 2 : 1);
+  const int mode = nearMode(a.ntri, ng, nearScalar);
   const uint32_t grid = t.nPlan + (c.n + 63u) / 64u;
   t.every = std::max(1u, grid / std::max(1u, t.nPlan));
   switch (beamsPerWave) {

@@ -35,7 +35,7 @@ void launch_sat(const uint32_t *cellStart, const Grid &g, uint32_t *sat, hipStre
 void launch_reorder(const gvpm_photon_soa &raw, const uint32_t *keys, const uint32_t *rank, const uint32_t *cellStart,
                     uint32_t n, const gvpm_params &cfg, const float4 *bvh, const float4 *tri4, uint32_t ntri, float dmax,
                     const NearGrid &ng, uint32_t *nearExt, uint32_t extCap, float4 *hot, float4 *cold, uint32_t *overflow,
-                    uint32_t *origIdx, const uint32_t *sub, uint32_t ncells, hipStream_t s);
+                    uint32_t *origIdx, const uint32_t *sub, uint32_t ncells, hipStream_t s, bool nearScalar = true);
 void launch_near_grid(const float4 *tri4, uint32_t ntri, const NearGrid &g, float reach, uint32_t *counts, uint32_t *tris, int mode,
                       hipStream_t s);
 void launch_segment_start(const uint32_t *keys, uint32_t n, uint32_t nseg, uint32_t shift, uint32_t *start,
@@ -59,7 +59,7 @@ void launch_beam_near_hist(const float4 *cold, uint32_t n, uint32_t ntri, uint32
 void launch_build_chain(ChainArgs c, const GatherArgs &a, const gvpm_photon_soa &raw, int beamsPerWave, uint32_t target, uint4 *items,
                         uint2 *itemOff, uint32_t itemCap, float dmax, const NearGrid &ng, uint32_t extCap, uint32_t *origIdx,
                         uint32_t *hostOut, bool initBuckets, hipStream_t s, uint32_t pairCapBlocks = 0xFFFFFFFFu, uint32_t unitCap = 0,
-                        uint32_t unitPairs = 1, bool fullVis = false, bool planGroups = true);
+                        uint32_t unitPairs = 1, bool fullVis = false, bool planGroups = true, bool nearScalar = true);
 // gather_bre.hip
 void launch_apply_host_shifts(const GatherArgs &a, const gvpm_host_shift *results, uint32_t n, hipStream_t s);
 void launch_plan_bre(const GatherArgs &a, int beamsPerWave, uint32_t ntiles, uint32_t target, uint4 *items,
@@ -342,6 +342,7 @@ struct gvpm_context {
   NearGrid nearGrid;
   float nearGridReach = -1.f;
   bool useNearGrid = true;  // GVPM_NEAR_GRID=0: the BVH point query instead (kept as the cross-check of the grid)
+  bool nearScalar = true;   // GVPM_NEAR_SCALAR=0: small scenes' linear scan with per-lane vector loads (the cross-check of the scalar one)
 
   // Host uploads land in a ring of three staging slots per kind, through a copy stream of their own: the copy of
   // step N+1 (or, prefetched, N+2) then runs while the kernels of step N still read theirs.  A slot's `copied` event

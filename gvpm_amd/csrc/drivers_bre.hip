@@ -275,7 +275,7 @@ int launchBuildAndPlan(BreStep &s) {
                        !h->bs->bucketsInit, h->bstream,
                        optimistic ? (refuse ? 0u : (uint32_t)std::min<size_t>((h->bs->pairs.cap - 64u) / 64u, 0xFFFFFFF0u)) : 0xFFFFFFFFu,
                        optimistic && h->evalUnits ? (uint32_t)std::min<size_t>(h->bs->units.cap / 2u, 0x3FFFFFFFu) : 0u, eval_unit_pairs(),
-                       fullVisOpt, h->planGroups);
+                       fullVisOpt, h->planGroups, h->nearScalar);
     h->bs->bucketsInit = true;
     s.chainRan = true;
     if (optimistic) {

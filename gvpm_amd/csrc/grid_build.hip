@@ -338,14 +338,17 @@ void launch_cell_count(const float *pos, uint32_t n, const Grid &g, uint32_t *ke
 void launch_reorder(const gvpm_photon_soa &raw, const uint32_t *keys, const uint32_t *rank, const uint32_t *cellStart,
                     uint32_t n, const gvpm_params &cfg, const float4 *bvh, const float4 *tri4, uint32_t ntri, float dmax,
                     const NearGrid &ng, uint32_t *nearExt, uint32_t extCap, float4 *hot, float4 *cold, uint32_t *overflow,
-                    uint32_t *origIdx, const uint32_t *sub, uint32_t ncells, hipStream_t s) {
+                    uint32_t *origIdx, const uint32_t *sub, uint32_t ncells, hipStream_t s, bool nearScalar) {
   const RawPhotons r = rawOf(raw);
 #define GVPM_REORDER(M) \
   hipLaunchKernelGGL(reorder_kernel<M>, dim3((n + 63) / 64), dim3(64), 0, s, r, keys, rank, cellStart, n, cfg, bvh, tri4, ntri, \
                      dmax, ng, nearExt, extCap, hot, cold, overflow, origIdx, sub, ncells)
-  if (ntri <= 64u) GVPM_REORDER(0);
-  else if (ng.start) GVPM_REORDER(2);
-  else GVPM_REORDER(1);
+  switch (nearMode(ntri, ng, nearScalar)) {
+    case NEAR_SCAN_SCALAR: GVPM_REORDER(NEAR_SCAN_SCALAR); break;
+    case NEAR_SCAN_VECTOR: GVPM_REORDER(NEAR_SCAN_VECTOR); break;
+    case NEAR_GRID: GVPM_REORDER(NEAR_GRID); break;
+    default: GVPM_REORDER(NEAR_BVH); break;
+  }
 #undef GVPM_REORDER
 }
 

@@ -77,10 +77,10 @@ __device__ __forceinline__ void reorderBody(const RawPhotons &r, const uint32_t 
     stg[t][3] = ld3(r.parent_pos, src, r.parent_rr[src]);
     q4 = ld3(r.parent_n, src, r.parent_g[src]);
     const f3 P = mk3(r.parent_pos[3 * (size_t)src], r.parent_pos[3 * (size_t)src + 1], r.parent_pos[3 * (size_t)src + 2]);
-    uint32_t w0, w1, w2;
     const f3 PN = mk3(q4.x, q4.y, q4.z);
-    float cstar;
-    nearOccluders<MODE>(P, PN, bvh, tri4, ntri, dmax, ng, nearExt, extCap, cfg.epsilon, w0, w1, w2, cstar);
+    const NearList nl = nearOccluders<MODE>(P, PN, bvh, tri4, ntri, dmax, ng, nearExt, extCap, cfg.epsilon);
+    const uint32_t w0 = nl.w0, w1 = nl.w1, w2 = nl.w2;
+    const float cstar = nl.cstar;
     if ((w0 >> 24) == 0xFEu) atomicAdd(overflow, 1u);
     // (bit 15 of the COLD record's flags only -- the depth field's top bit, which the evaluation does not read: "word 2 of the
     // near list is the reach of the wall the parent sits behind"; the hot record the traversal filters by keeps the flags)

@@ -432,8 +432,23 @@ template <int B, uint32_t PLAN_STAGE = 512> struct PlanLds {
   float pb[8][B];
   uint32_t pvalid[B];
 };
+// Registers of the planners inside the build chain's tail kernel (round 24: at the 80 VGPRs that kernel is compiled for,
+// planBodyQ alone spilled 17 and planBody 7; LEAN below is planBody with the same cure, its own kernel keeps its code).
+// What is the same in every lane is said so (readfirstlane: an SGPR instead of a VGPR held across every loop); what is a
+// constant of the LANE (its group, its place in the group, the masks of both) is formed again where it is used, from a lane
+// index the compiler cannot see through -- hoisted to the kernel's entry, each such constant was a register, or a spill slot,
+// for the whole walk; the summed-volume table is read at 32-bit byte offsets from its uniform base (its entries number
+// less than 2^30: 10-bit cell coordinates) instead of through eight 64-bit per-lane pointers.
+__device__ __forceinline__ float uniformF32(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
+__device__ __forceinline__ int opaqueLane(int lane) {
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+__device__ __forceinline__ uint32_t ldU32At(const uint32_t *base, uint32_t byteOff) {
+  return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(base) + byteOff);
+}
 // bid / nblk: this wave's index among the planner's waves and their number (tiles are taken with stride nblk)
-template <int B, uint32_t PLAN_STAGE>
+template <int B, uint32_t PLAN_STAGE, bool LEAN = false>
 __device__ __forceinline__ void planBody(const GatherArgs &a, uint32_t ntiles, uint32_t target, uint4 *items, uint32_t *itemCount,
                                          uint2 *itemOff, uint32_t *blockTotal, uint32_t itemCap, uint32_t bid, uint32_t nblk,
                                          PlanLds<B, PLAN_STAGE> &L) {
@@ -481,6 +496,12 @@ __device__ __forceinline__ void planBody(const GatherArgs &a, uint32_t ntiles, u
     const RayReg base = loadBaseDirect<B>(a, setBase, nb, lane, bi);
     TileWalk w;
     tileSetupFrom(a, base, base.valid, w);
+    if constexpr (LEAN) {  // (tileSetupFrom's own expressions, held in SGPRs)
+      const float r = a.radius, eps = a.cfg.epsilon;
+      w.pad = uniformF32(r * 1.01f + 1e-6f);
+      w.t0 = uniformF32(eps - 2.f * r);
+      w.t1 = (w.base.len - eps) + uniformF32(2.f * r);
+    }
     if (w.bundleBad && lane == 0 && a.bundleFlag) atomicOr(a.bundleFlag, 1u);
     if (!w.any) continue;
     __syncthreads();
@@ -535,13 +556,14 @@ __device__ __forceinline__ void planBody(const GatherArgs &a, uint32_t ntiles, u
       // not span groups of 64 steps (tiles rarely have that many)
       const uint32_t incl = wave_scan_incl(cnt, lane);
       const uint32_t excl = incl - cnt;
+      const int ln = LEAN ? opaqueLane(lane) : lane;  // (LEAN: the masks below are formed here, not held from the kernel's entry)
       const uint32_t id = excl / target;
       const uint32_t idPrev = __shfl_up(id, 1, 64), idNext = __shfl_down(id, 1, 64);
-      const bool first = live && (lane == 0 || id != idPrev);
-      const bool liveNext = lane < 63 && step + 1 < nsteps;
+      const bool first = live && (ln == 0 || id != idPrev);
+      const bool liveNext = ln < 63 && step + 1 < nsteps;
       const bool closes = live && (!liveNext || idNext != id);
       const unsigned long long firstMask = __ballot(first);
-      const unsigned long long below = firstMask & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
+      const unsigned long long below = firstMask & (ln == 63 ? ~0ull : ((2ull << ln) - 1ull));
       const int fl = below ? 63 - __clzll(below) : 0;
       const uint32_t exclFirst = __shfl(excl, fl, 64);
       const int cAFirst = __shfl(cA, fl, 64);
@@ -573,7 +595,7 @@ __device__ __forceinline__ void planBody(const GatherArgs &a, uint32_t ntiles, u
       } else if (emitMask && !splitHeavy) {
         if (nStaged + 64u > PLAN_STAGE) flush();
         if (emit) {
-          const uint32_t k = nStaged + (uint32_t)__popcll(emitMask & ((1ull << lane) - 1ull));
+          const uint32_t k = nStaged + (uint32_t)__popcll(emitMask & ((1ull << ln) - 1ull));
           // (G-BRE: the chunk's ordinal rides on nb, for the traversal to find the chunk's boxes)
           stItem[k] = make_uint4(setBase, nb | ((setBase / B + tile) << 8), (uint32_t)cAFirst, (uint32_t)cAe);
           stStaged[k] = staged;
@@ -634,8 +656,9 @@ __device__ __forceinline__ void planBodyQ(const GatherArgs &a, uint32_t ntiles, 
   constexpr int G = 64 / B;
   auto &stItem = L.stItem;
   auto &stStaged = L.stStaged;
-  const int lane = threadIdx.x, q = lane / B, bl = lane % B;
-  const unsigned long long gm = (B == 64 ? ~0ull : ((1ull << (B & 63)) - 1ull) << (q * B));  // my group's lanes
+  const int lane = threadIdx.x;
+  // my group's lanes
+  auto groupMask = [](int q) { return B == 64 ? ~0ull : ((1ull << (B & 63)) - 1ull) << (q * B); };
   uint32_t nStaged = 0;  // wave-uniform
   auto flush = [&]() {
     __syncthreads();
@@ -664,17 +687,20 @@ __device__ __forceinline__ void planBodyQ(const GatherArgs &a, uint32_t ntiles, 
     __syncthreads();
   };
   const float r = a.radius, eps = a.cfg.epsilon;
+  const float padU = uniformF32(r * 1.01f + 1e-6f), t0U = uniformF32(eps - 2.f * r), r2U = uniformF32(2.f * r);
   // (group q of wave `bid` takes the tiles bid + (trip * G + q) * nblk: the tiles one wave of planBody takes one after the
   // other -- the items then come out in the order they always had.  With ADJACENT tiles side by side the item list runs over the
   // image row by row and the traversal, whose workgroup i takes item i, lost a fifth of its speed: 0.33 -> 0.40 ms alone.)
   for (uint32_t t0 = bid; t0 < ntiles; t0 += nblk * G) {
-    const uint32_t tile = t0 + (uint32_t)q * nblk;
+    const uint32_t tile = t0 + (uint32_t)(opaqueLane(lane) / B) * nblk;
     const bool haveTile = tile < ntiles;
     const uint32_t tileBeg = haveTile ? a.tileStart[tile] : 0u, tileEnd = haveTile ? a.tileStart[tile + 1] : 0u;
     for (uint32_t setBase = tileBeg; __ballot(setBase < tileEnd) != 0ull; setBase += B) {
       const uint32_t nb = setBase < tileEnd ? min((uint32_t)B, tileEnd - setBase) : 0u;
       BaseInfo bi;
       const RayReg base = loadBaseDirect<B>(a, setBase, nb, lane, bi);
+      const int ln1 = opaqueLane(lane), q = ln1 / B, bl = ln1 % B;
+      const unsigned long long gm = groupMask(q);
       // ---- tileSetupFrom over the group ----
       const bool beamValid = base.valid;
       int A;
@@ -701,9 +727,9 @@ __device__ __forceinline__ void planBodyQ(const GatherArgs &a, uint32_t ntiles, 
       w.dimU = U == 0 ? a.grid.dim[0] : (U == 1 ? a.grid.dim[1] : a.grid.dim[2]);
       w.dimV = V == 0 ? a.grid.dim[0] : (V == 1 ? a.grid.dim[1] : a.grid.dim[2]);
       w.dimA = dimA;
-      w.pad = r * 1.01f + 1e-6f;
-      w.t0 = eps - 2.f * r;
-      w.t1 = (base.len - eps) + 2.f * r;
+      w.pad = padU;
+      w.t0 = t0U;
+      w.t1 = (base.len - eps) + r2U;
       float aLo = INFINITY, aHi = -INFINITY;
       if (beamValid) {
         const float e0 = w.oA + w.dA * w.t0, e1 = w.oA + w.dA * w.t1;
@@ -732,6 +758,7 @@ __device__ __forceinline__ void planBodyQ(const GatherArgs &a, uint32_t ntiles, 
       for (int o = 32; o >= B; o >>= 1) maxSteps = max(maxSteps, __shfl_xor(maxSteps, o, 64));
       const uint32_t chunkOrd = setBase / B + tile;
       for (int sbase = 0; sbase < maxSteps; sbase += B) {
+        const int ln2 = opaqueLane(lane), q = ln2 / B, bl = ln2 % B;
         const int step = sbase + bl;
         const bool live = step < nsteps;
         const int cA = w.cA0 + step * w.K, cAe = min(cA + w.K - 1, w.cA1);
@@ -758,28 +785,31 @@ __device__ __forceinline__ void planBodyQ(const GatherArgs &a, uint32_t ntiles, 
             // photons in the box from the summed-volume table: 8 reads
             const uint32_t nx1 = a.grid.dim[0] + 1, ny1 = a.grid.dim[1] + 1;
             const uint32_t *T = a.sat;
-            const size_t z0 = (size_t)bx.bz0 * ny1, z1 = (size_t)(bx.bz1 + 1) * ny1;
-            const uint32_t y0 = bx.by0, y1 = bx.by1 + 1, x0 = bx.bx0, x1 = bx.bx1 + 1;
-            cnt = (T[(z1 + y1) * nx1 + x1] - T[(z1 + y1) * nx1 + x0] - T[(z1 + y0) * nx1 + x1] + T[(z1 + y0) * nx1 + x0]) -
-                  (T[(z0 + y1) * nx1 + x1] - T[(z0 + y1) * nx1 + x0] - T[(z0 + y0) * nx1 + x1] + T[(z0 + y0) * nx1 + x0]);
+            const uint32_t z0 = (uint32_t)bx.bz0 * ny1, z1 = (uint32_t)(bx.bz1 + 1) * ny1;
+            const uint32_t y0 = bx.by0, y1 = bx.by1 + 1, x0 = 4u * (uint32_t)bx.bx0, x1 = 4u * (uint32_t)(bx.bx1 + 1);
+            const uint32_t r11 = (z1 + y1) * nx1 * 4u, r10 = (z1 + y0) * nx1 * 4u, r01 = (z0 + y1) * nx1 * 4u, r00 = (z0 + y0) * nx1 * 4u;
+            cnt = (ldU32At(T, r11 + x1) - ldU32At(T, r11 + x0) - ldU32At(T, r10 + x1) + ldU32At(T, r10 + x0)) -
+                  (ldU32At(T, r01 + x1) - ldU32At(T, r01 + x0) - ldU32At(T, r00 + x1) + ldU32At(T, r00 + x0));
           }
         }
         // greedy cut over the group's B steps
+        const int ln3 = opaqueLane(lane), bl3 = ln3 % B;
+        const unsigned long long gm3 = groupMask(ln3 / B);
         uint32_t incl = cnt;
 #pragma unroll
         for (int o = 1; o < B; o <<= 1) {
           const uint32_t nv = __shfl_up(incl, o, 64);
-          if (bl >= o) incl += nv;
+          if (bl3 >= o) incl += nv;
         }
         const uint32_t excl = incl - cnt;
         const uint32_t id = excl / target;
         const uint32_t idPrev = __shfl_up(id, 1, 64), idNext = __shfl_down(id, 1, 64);
-        const bool first = live && (bl == 0 || id != idPrev);
-        const bool liveNext = bl < B - 1 && step + 1 < nsteps;
+        const bool first = live && (bl3 == 0 || id != idPrev);
+        const bool liveNext = bl3 < B - 1 && step + 1 < nsteps;
         const bool closes = live && (!liveNext || idNext != id);
-        const unsigned long long firstMask = __ballot(first) & gm;
-        const unsigned long long below = firstMask & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
-        const int fl = below ? 63 - __clzll(below) : lane;
+        const unsigned long long firstMask = __ballot(first) & gm3;
+        const unsigned long long below = firstMask & (ln3 == 63 ? ~0ull : ((2ull << ln3) - 1ull));
+        const int fl = below ? 63 - __clzll(below) : ln3;
         const uint32_t exclFirst = __shfl(excl, fl, 64);
         const int cAFirst = __shfl(cA, fl, 64);
         const uint32_t staged = incl - exclFirst;
@@ -788,7 +818,7 @@ __device__ __forceinline__ void planBodyQ(const GatherArgs &a, uint32_t ntiles, 
         if (emitMask) {
           if (nStaged + 64u > PLAN_STAGE) flush();
           if (emit) {
-            const uint32_t k = nStaged + (uint32_t)__popcll(emitMask & ((1ull << lane) - 1ull));
+            const uint32_t k = nStaged + (uint32_t)__popcll(emitMask & ((1ull << ln3) - 1ull));
             stItem[k] = make_uint4(setBase, nb | (chunkOrd << 8), (uint32_t)cAFirst, (uint32_t)cAe);
             stStaged[k] = staged;
           }
